@@ -12,10 +12,21 @@ Multi-GPU: one process per GPU (torch.distributed.run), each rank verifies its
 own independent 1M batch (weak scaling, no data-path collective); CPU-side gloo
 only for the barrier and the max-over-ranks time.
 
-Extras on the JSON line: roofline (INT32 VALU, v_mad_u64_u32 issue peak),
-cpu_baseline (the oracle, a C restatement, on this host's cores, N=1 only),
-p50/p99 batch latency of 65,536-txn batches through the async PCIe path, and
-the PCIe-inclusive pipelined throughput.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the
+headline figure needs: it generates and uploads the batch, warms up, times the
+N steps and prints the JSON line (metric, value, unit, ms_per_step, ...).
+`--dump-outputs DIR` also writes what the last timed step computed -- the
+per-transaction codes a caller of the timed path reads back -- as
+DIR/codes.npy (float32); the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
+
+`--full` adds everything else to the line: the self-check of the codes, the
+roofline from an isolated HIP-event-timed verify (INT32 VALU, v_mad_u64_u32
+issue peak), cpu_baseline (the oracle, a C restatement, on this host's cores,
+N=1 only) and the full-size parity against it, p50/p99 batch latency of
+65,536-txn batches through the async PCIe path, the PCIe-inclusive pipelined
+throughput, the cfg3 / key-pool / host-fed / adversarial / GPU-ingest lines
+and the cfg5 verify-tile lines.
 """
 import argparse
 import json
@@ -66,7 +77,15 @@ def parse():
     ap.add_argument("--latency-batches", type=int, default=1000)   # >=1000 after 100 warm-up
     ap.add_argument("--latency-batch", type=int, default=65536)
     ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="txns timed on the CPU oracle (bounded sample)")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed device-resident loop (profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed loop: self-check, roofline (an isolated HIP-event-timed verify), latency and "
+                         "PCIe legs, tile lines, cfg3 / key-pool / host-fed / adversarial / ingest lines, CPU baseline "
+                         "and full-size parity (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the last step's outputs (the batch's per-txn codes) as "
+                         "DIR/codes.npy, float32")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: only the timed loop and its roofline (profiling); a plain run has no extras")
     ap.add_argument("--hw-queues", type=int, default=HW_QUEUES,
                     help="GPU_MAX_HW_QUEUES of this process (applied before HIP starts; the tile child uses "
                          f"{TILE_HW_QUEUES})")
@@ -997,8 +1016,9 @@ def key_cache_rate(eng, device, n_txn, seed, pool=4096):
 
 def main():
     args = parse()
+    extras_on = args.full and not args.no_extras
     dist = Dist()
-    cpus = dist.cpus()
+    cpus = dist.cpus() if extras_on else None      # only the extras pin threads (picking idle cores samples /proc/stat)
     from firedancer_amd import VerifyEngine, _lib, workload
 
     progress("generating the cfg1 batch", dist.rank)
@@ -1011,9 +1031,9 @@ def main():
     # process's engines open beside them, one tile ran 34.5 M txn/s against
     # 38 M alone; profiles/r04/tile_run_order.md), and a rank and its child
     # are never two GPU processes at once
-    cfg3 = workload.cfg3(args.cfg3_txns, seed=workload.CFG3_SEED + dist.rank) if args.cfg3_txns else None
+    cfg3 = workload.cfg3(args.cfg3_txns, seed=workload.CFG3_SEED + dist.rank) if args.cfg3_txns and extras_on else None
     tl = None
-    if args.tile and not args.no_extras:
+    if args.tile and extras_on:
         cfg3_tile = (workload.cfg3(args.tile_cfg3_txns, seed=workload.CFG3_SEED + 0x100 + dist.rank)
                      if args.tile_cfg3_txns else None)
         tl = tile_lines(dist.local_rank, arena, txns, modes, cpus, cfg3=cfg3_tile, world=dist.world)
@@ -1051,7 +1071,7 @@ def main():
     for i in range(max(args.warmup, len(batches))):
         batches[i % len(batches)].verify()
     eng.sync()
-    self_check = all(bool(((b.codes() == 0) == (modes == 0)).all()) for b in batches)
+    self_check = all(bool(((b.codes() == 0) == (modes == 0)).all()) for b in batches) if args.full else None
 
     dist.barrier()
     eng.sync()
@@ -1063,13 +1083,38 @@ def main():
     dist.barrier()
     value, dt_max = aggregate(dist, n_sig, args.steps, dt)
 
-    # live HIP-event timing of the verify pipeline (same stream, same batch)
-    wall_ms, kv_ms, kc_ms = batch.time(max(3, min(args.steps, 10)))
-    achieved = n_sig * MADS_PER_SIG / (kv_ms * 1e-3) / 1e12
-    traffic, traffic_src = pmc_traffic()
+    if args.dump_outputs:
+        # what the last timed step left for its caller: the codes of the batch
+        # it verified (4 B x txns as float32, 4 MB at the default size)
+        last = batches[(args.steps - 1) % len(batches)] if args.steps else batch
+        out_dir = args.dump_outputs if dist.world == 1 else os.path.join(args.dump_outputs, f"rank{dist.rank}")
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "codes.npy"), last.codes().astype(np.float32))
+
+    roofline = {"bound": "valu", "peak": round(VALU_MAD_PEAK_TOPS, 2), "unit": "TOP/s",
+                "peak_measured": VALU_MAD_MEASURED_TOPS,
+                "frac_overlapped": round(value / dist.world * MADS_PER_SIG / 1e12 / VALU_MAD_PEAK_TOPS, 4),
+                "note": f"INT32 v_mad_u64_u32 ops: {MADS_PER_SIG} algorithmic mads/sig x {n_sig} sigs over the timed "
+                        "steps (frac_overlapped, against the nominal issue peak); --full adds the isolated "
+                        f"{VERIFY_KERNEL}'s achieved / frac"}
+    kv_ms = kc_ms = None
+    if args.full:
+        # live HIP-event timing of the verify pipeline (same stream, same batch)
+        wall_ms, kv_ms, kc_ms = batch.time(max(3, min(args.steps, 10)))
+        achieved = n_sig * MADS_PER_SIG / (kv_ms * 1e-3) / 1e12
+        traffic, traffic_src = pmc_traffic()
+        roofline.update({
+            "achieved": round(achieved, 3), "frac": round(achieved / VALU_MAD_PEAK_TOPS, 4), "traffic": traffic,
+            "frac_measured": round(achieved / VALU_MAD_MEASURED_TOPS, 4),
+            "peak_note": "frac uses the nominal v_mad_u64_u32 issue peak (39.32 T/s); frac_measured "
+                         "the instruction's measured rate (33.88 T/s, profiles/r01_ubench_int.jsonl)",
+            "note": f"INT32 v_mad_u64_u32 ops: {MADS_PER_SIG} algorithmic mads/sig x {n_sig} sigs / mean "
+                    f"{VERIFY_KERNEL} ({_lib.lib().fdgpu_kernel_path().decode()}) time "
+                    f"{kv_ms:.3f} ms (HIP events, compute stream); combine kernel "
+                    f"{kc_ms:.4f} ms; traffic source {traffic_src}"})
 
     extras = {}
-    if not args.no_extras:
+    if extras_on:
         progress("latency and PCIe-inclusive legs", dist.rank)
         extras = latency_and_pcie(eng, arena, txns, args.latency_batch, args.latency_batches,
                                   pin_cpu=(cpus[1] if len(cpus) > 1 else cpus[0]) if cpus else None)
@@ -1109,7 +1154,7 @@ def main():
                                       (kv_ms + kc_ms) / n_sig, cpus))
     cpu = None
     parity = {}
-    if not args.no_extras:
+    if extras_on:
         # full-size cfg2 parity: every GPU code of this rank's batch against the
         # oracle (rank 0 also times that oracle run as the CPU baseline)
         progress("parity against the oracle / CPU baseline", dist.rank)
@@ -1123,13 +1168,13 @@ def main():
         mism = int((gpu_codes[:n_chk] != cpu_codes).sum())
         parity = {"parity_checked_txns": int(dist.sum(n_chk)), "parity_mismatches": int(dist.sum(mism)),
                   "parity_codes": {int(c): int(k) for c, k in zip(*np.unique(cpu_codes, return_counts=True))}}
-    if not args.no_extras:
+    if extras_on:
         progress("GPU ingest", dist.rank)
         extras.update(gpu_ingest(eng, arena, txns, batch.codes()))
     for b in batches:
         b.free()
     eng.close()
-    self_ok = dist.sum(1 if self_check else 0) == dist.world
+    self_ok = (dist.sum(1 if self_check else 0) == dist.world) if args.full else None
 
     if dist.rank == 0:
         line = {
@@ -1149,18 +1194,8 @@ def main():
                                    "corrupted, device-resident batch, full verify + per-txn combine per step",
                        "sigs_per_gpu_per_step": n_sig, "parallelism": f"dp{dist.world} (independent per-GPU batches)",
                        "queues": len(batches)},
-            "roofline": {"bound": "valu", "achieved": round(achieved, 3), "peak": round(VALU_MAD_PEAK_TOPS, 2),
-                         "unit": "TOP/s", "frac": round(achieved / VALU_MAD_PEAK_TOPS, 4),
-                         "traffic": traffic,
-                         "peak_measured": VALU_MAD_MEASURED_TOPS,
-                         "frac_measured": round(achieved / VALU_MAD_MEASURED_TOPS, 4),
-                         "peak_note": "frac uses the nominal v_mad_u64_u32 issue peak (39.32 T/s); frac_measured "
-                                      "the instruction's measured rate (33.88 T/s, profiles/r01_ubench_int.jsonl)",
-                         "frac_overlapped": round(value / dist.world * MADS_PER_SIG / 1e12 / VALU_MAD_PEAK_TOPS, 4),
-                         "note": f"INT32 v_mad_u64_u32 ops: {MADS_PER_SIG} algorithmic mads/sig x {n_sig} sigs / mean "
-                                 f"{VERIFY_KERNEL} ({_lib.lib().fdgpu_kernel_path().decode()}) time "
-                                 f"{kv_ms:.3f} ms (HIP events, compute stream); combine kernel "
-                                 f"{kc_ms:.4f} ms; traffic source {traffic_src}"},
+            "roofline": roofline,
+            "full": bool(args.full),
             "cpu_baseline": cpu,
             "self_check_codes": self_ok,
             "build": build_info,

@@ -44,6 +44,7 @@ import json
 import os
 import sys
 import time
+import traceback
 
 import numpy as np
 
@@ -335,26 +336,41 @@ def main(argv=None, make_verifiers=gpu_verifiers):
     if log_f:
         import zipfile  # noqa: F401  (np.savez imports it on first use)
     try:
-        res = serve(a.in_paths, a.out_paths, vers, cnts, timeout_s=a.timeout, idle_s=a.idle_ms / 1e3,
-                    cpus=[int(x) for x in a.cpus.split(",") if x] or None, ready_file=a.ready_file or None,
-                    log_max=(sum(cnts) + 16) if a.log else 0, hashmap_seed=a.seed, batch_txn_max=a.batch,
-                    inflight_max=a.inflight, batch_wait_us=a.wait_us, batch_sig_max=a.batch_sig_max,
-                    gpu_parse=a.gpu_parse, flow_control=bool(a.out_flow_control), rr_idx=a.rr_idx, rr_cnt=a.rr_cnt,
-                    sandbox=a.sandbox, **guard)
-    finally:
-        close()
-    res.update(info)
-    if log_f:
-        logs = res.pop("logs")
-        np.savez(log_f, **{f"seq{k}": s for k, (s, _) in enumerate(logs)},
-                 **{f"code{k}": cd for k, (_, cd) in enumerate(logs)})
-        log_f.close()
-    line = json.dumps(res)
-    if res_f:
-        res_f.write(line + "\n")
-        res_f.close()
-    print(line, flush=True)
-    return 0
+        try:
+            res = serve(a.in_paths, a.out_paths, vers, cnts, timeout_s=a.timeout, idle_s=a.idle_ms / 1e3,
+                        cpus=[int(x) for x in a.cpus.split(",") if x] or None, ready_file=a.ready_file or None,
+                        log_max=(sum(cnts) + 16) if a.log else 0, hashmap_seed=a.seed, batch_txn_max=a.batch,
+                        inflight_max=a.inflight, batch_wait_us=a.wait_us, batch_sig_max=a.batch_sig_max,
+                        gpu_parse=a.gpu_parse, flow_control=bool(a.out_flow_control), rr_idx=a.rr_idx, rr_cnt=a.rr_cnt,
+                        sandbox=a.sandbox, **guard)
+        finally:
+            close()
+        res.update(info)
+        if log_f:
+            logs = res.pop("logs")
+            np.savez(log_f, **{f"seq{k}": s for k, (s, _) in enumerate(logs)},
+                     **{f"code{k}": cd for k, (_, cd) in enumerate(logs)})
+            log_f.close()
+        line = json.dumps(res)
+        if res_f:
+            res_f.write(line + "\n")
+            res_f.close()
+        print(line, flush=True)
+        rc = 0
+    except Exception:
+        if a.sandbox != 1:
+            raise
+        traceback.print_exc()
+        rc = 1
+    if a.sandbox == 1:
+        # the process leaves from inside the enforced policy without the
+        # interpreter's finalisation: whatever else would run there (an atexit
+        # handler, a site hook of the host's) may open a file, and the policy
+        # answers that by killing the process after its result is out
+        sys.stdout.flush()
+        sys.stderr.flush()
+        os._exit(rc)
+    return rc
 
 
 if __name__ == "__main__":

@@ -6,6 +6,8 @@ GPU box."""
 import os
 import sys
 
+import pytest
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
@@ -71,6 +73,60 @@ def test_parent_rank_starts_no_hip_before_its_tile_child():
     assert main.index("node_lines(") < main.index("require_product_build(")
     assert "_lib.lib()" not in main[:main.index("require_product_build(")]
     assert main.index("fdgpu_device_count()") < main.index("VerifyEngine(")
+
+
+def test_plain_and_full_options(monkeypatch):
+    """A plain run is the timed loop alone; everything else on the line sits
+    behind --full (off by default), and --dump-outputs names the directory
+    the last step's codes go to."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.gpus, a.steps, a.warmup) == (1, 7, 2) and a.full is False and a.dump_outputs == ""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "/tmp/o"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "/tmp/o"
+    # every extra leg of main() is gated on --full
+    src = open(os.path.join(REPO, "bench.py")).read()
+    main = src[src.index("def main():"):]
+    assert "extras_on = args.full and not args.no_extras" in main
+    for leg in ("tile_lines(", "latency_and_pcie(", "latency_frag_io(", "sync_latency(", "cfg3_rate(",
+                "key_cache_rate(", "host_fed(", "adversarial(", "cpu_baseline(", "gpu_ingest(", "orc.verify_txns("):
+        head = main[:main.index(leg)]
+        gate = head.rindex("\n    if ")                     # the enclosing top-level condition of main()
+        assert "extras_on" in head[gate:head.index("\n", gate + 1)], leg
+    head = main[:main.index("batch.time(")]
+    assert head[head.rindex("\n    if "):].startswith("\n    if args.full:")
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_last_step_codes(tmp_path, oracle):
+    """`bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR` on a small
+    batch: one JSON line with the headline fields and none of the --full
+    legs, and DIR/codes.npy (float32) holding the timed path's codes -- equal
+    to the oracle's over the same seeded txns."""
+    import json
+    import subprocess
+    import numpy as np
+    from firedancer_amd import workload
+    n = 3000
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--txns", str(n), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=120, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "verified ed25519 sigs/sec (node)" and d["unit"] == "sigs/s" and d["dtype"] == "u32"
+    assert d["higher_is_better"] is True and d["steps"] == 3 and d["full"] is False
+    # value = sigs per step / the step time (ms_per_step is rounded to 1e-4 ms, value to 0.1)
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) <= d["value"] * 1e-4 / d["ms_per_step"] + 1
+    assert d["cpu_baseline"] is None and "parity_mismatches" not in d and "achieved" not in d["roofline"]
+    assert not any(k.startswith(("tile_", "adv_", "host_fed_", "cfg3_", "gpu_ingest_", "sync_")) for k in d)
+    codes = np.load(tmp_path / "out" / "codes.npy")
+    assert codes.dtype == np.float32 and codes.shape == (n,)
+    arena, txns, _ = workload.cfg1(n, seed=workload.CFG1_SEED)
+    assert (codes == oracle.verify_txns(arena, txns).astype(np.float32)).all()
 
 
 def test_idle_first_counts_smt_siblings(monkeypatch):

@@ -258,6 +258,24 @@ def test_engine_process_sandboxed_cpu(tmp_path, oracle):
     assert res["engine"]["sandbox"] == 2 and res["engine"]["sandbox_refused"] == [], res["engine"]["sandbox_refused"]
 
 
+def test_engine_process_sandboxed_leaves_without_finalisation_cpu(tmp_path, oracle):
+    """Inside the enforced policy (--sandbox 1) the engine process leaves
+    once its result is out, without the interpreter's finalisation: an exit
+    handler that opens a file -- as a host's site hook may register in every
+    Python process -- never runs, where running it would be a refused open
+    that kills the process (SIGSYS) after all its work.  Without the policy
+    the same handler runs."""
+    ps = _mixed_stream(300, seed=79)
+    worker = CPU_ENGINE[1]
+    for sandbox, ran in ((1, False), (0, True)):
+        mark = tmp_path / f"exit_handler_ran_{sandbox}"
+        code = (f"import atexit, runpy; atexit.register(lambda: open({str(mark)!r}, 'w').close()); "
+                f"runpy.run_path({worker!r}, run_name='__main__')")
+        res, _ = _xproc_vs_model(tmp_path, ps, oracle, engine_cmd=[sys.executable, "-c", code], depth=1 << 12,
+                                 batch=64, inflight=3, sandbox=sandbox, dedup=False)
+        assert res["engine"]["sandbox"] == sandbox and mark.exists() == ran
+
+
 def test_engine_process_two_tiles_cpu(tmp_path, oracle):
     """Two verify tiles in the engine process take the round-robin shares of
     the link (fd_verify.c:46), each into its own out link."""

@@ -8,7 +8,7 @@ echo "[$(date +%T)] smoke"
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { tail -30 $out/smoke.log; exit 1; }
 tail -2 $out/smoke.log
 echo "[$(date +%T)] bench"
-timeout -k 10 900 python3 bench.py > $out/bench.json 2> $out/bench.err || { tail -30 $out/bench.err; cat $out/bench.json; exit 1; }
+timeout -k 10 900 python3 bench.py --full > $out/bench.json 2> $out/bench.err || { tail -30 $out/bench.err; cat $out/bench.json; exit 1; }
 python3 -c "
 import json; d=json.load(open('$out/bench.json'))
 print(d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('parity_mismatches'))

@@ -20,7 +20,7 @@ if has tests; then
 fi
 if has bench; then
   step bench
-  timeout -k 10 600 python3 bench.py > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; cat $out/bench.json; exit 1; }
+  timeout -k 10 600 python3 bench.py --full > $out/bench.json 2> $out/bench.err || { tail $out/bench.err; cat $out/bench.json; exit 1; }
   cat $out/bench.json
 fi
 if has trace; then

@@ -63,7 +63,7 @@ def main():
                 end = max(end, e2)
         pipes.append((s, end, q))
     # bench.py: max(warmup, queues) warm-up verifies, the `steps` timed ones,
-    # then batch.time()'s max(3, min(steps, 10)) single-stream launches
+    # then (--full only) batch.time()'s max(3, min(steps, 10)) single-stream launches
     w = max(int(bench["warmup"]), int(bench["config"].get("queues") or 1))
     timed = pipes[w:w + steps]
     span = (max(e for _, e, _ in timed) - min(s for s, _, _ in timed)) / 1e6
