@@ -543,6 +543,15 @@ static uint32_t ring_kflags(fdgpu_engine_t *e, Slot *s, uint64_t n_sig) {
   return f;
 }
 
+/* The fault-injection environment, read by the engine at open and reported by
+   fdgpu_build_info: FDGPU_DEBUG_DROP_FLAG=1 (completion flags dropped) and
+   FDGPU_DEBUG_FAIL_MERGE=k (the k-th merge launch fails). */
+struct DebugEnv { bool drop_flag; int fail_merge; };
+static DebugEnv debug_env() {
+  const char *df = getenv("FDGPU_DEBUG_DROP_FLAG"), *fm = getenv("FDGPU_DEBUG_FAIL_MERGE");
+  return {df && df[0] == '1', fm ? atoi(fm) : 0};
+}
+
 extern "C" {
 
 char const *fdgpu_last_error(void) { return g_err.c_str(); }
@@ -591,10 +600,10 @@ fdgpu_engine_t *fdgpu_engine_open(int device, fdgpu_cfg_t const *cfg_in) {
   /* completion words: probe that a stream write reaches pinned host memory
      (FDGPU_POLL_EVENT=1 keeps hipEventQuery polling) */
   {
-    const char *pe = getenv("FDGPU_POLL_EVENT"), *df = getenv("FDGPU_DEBUG_DROP_FLAG");
-    e->drop_flag = df && df[0] == '1';
-    const char *fm = getenv("FDGPU_DEBUG_FAIL_MERGE");
-    e->fail_merge_at = fm ? (uint32_t)atoi(fm) : 0u;
+    const char *pe = getenv("FDGPU_POLL_EVENT");
+    const DebugEnv dbg = debug_env();
+    e->drop_flag = dbg.drop_flag;
+    e->fail_merge_at = (uint32_t)dbg.fail_merge;
     Slot &s0 = e->slots[0];
     if (!(pe && pe[0] == '1') && hipStreamWriteValue32(s0.stream, s0.d_flag, 0x5a5a5a5au, 0) == hipSuccess &&
         hipStreamSynchronize(s0.stream) == hipSuccess)
@@ -831,12 +840,10 @@ char const *fdgpu_build_info(void) {
   static thread_local char buf[512];
   char kb[256];
   const int kprod = fdgpu_kernel_build_info(kb, sizeof kb);
-  const char *df = getenv("FDGPU_DEBUG_DROP_FLAG");      /* fault injection: completion flags dropped */
-  const char *fm = getenv("FDGPU_DEBUG_FAIL_MERGE");     /* fault injection: a merge launch fails */
-  const int drop = df && df[0] == '1', fail_merge = fm ? atoi(fm) : 0;
-  const int prod = kprod && FDGPU_COPY_THREADS_N == 4 && !drop && !fail_merge;
+  const DebugEnv dbg = debug_env();
+  const int prod = kprod && FDGPU_COPY_THREADS_N == 4 && !dbg.drop_flag && !dbg.fail_merge;
   snprintf(buf, sizeof buf, "{%s,\"copy_threads\":%d,\"debug_drop_flag\":%d,\"debug_fail_merge\":%d,\"product\":%d}",
-           kb, (int)FDGPU_COPY_THREADS_N, drop, fail_merge, prod);
+           kb, (int)FDGPU_COPY_THREADS_N, (int)dbg.drop_flag, dbg.fail_merge, prod);
   return buf;
 }
 
@@ -1355,11 +1362,11 @@ int merge_kick_queue(fdgpu_engine_t *e, bool force) {
       const uint32_t grid = (uint32_t)((s->m_bound + FDGPU_BLOCK - 1) / FDGPU_BLOCK);
       uint32_t slow = grid < e->resident_blocks ? grid : e->resident_blocks;
       if (slow > FDGPU_FULL_BLOCKS) slow = FDGPU_FULL_BLOCKS;
-      uint32_t *cnt = fdgpu_verify_cnt_word(s->d_ws, (uint32_t)s->m_bound);
+      const fdgpu_ws_layout_t l = fdgpu_ws_layout(s->d_ws, s->m_bound);
       st_rlx(s->k_sigs, s->m_bound);
       st_rlx(s->k_lanes, s->m_bound);          /* one lane each: the merged launch never takes the pair kernel */
       tab[j] = fdgpu_mbatch_t{s->m_arena, s->d_sigs, s->d_io_cnt, s->d_ws, s->d_sig_codes,
-                              cnt - (size_t)grid * FDGPU_BLOCK, cnt, (uint32_t)s->m_bound, slow};
+                              l.queue, l.cnt, (uint32_t)s->m_bound, slow};
       grid_max = grid > grid_max ? grid : grid_max;
       slow_max = slow > slow_max ? slow : slow_max;
     }
@@ -1536,7 +1543,7 @@ int64_t fdgpu_submit_frags_io(fdgpu_engine_t *e, fdgpu_frag_io_t const *fio, uin
                                        dma ? (const uint64_t *)(s->d_ioh + rtab_at) : nullptr, (uint32_t)n,
                                        arena, s->d_fxio, s->d_txn_out, s->d_txn_sz, s->d_sigs, s->d_txns,
                                        s->d_io_cnt,
-                                       zero_cnt ? fdgpu_verify_cnt_word(s->d_ws, (uint32_t)bound) : nullptr, s->stream),
+                                       zero_cnt ? fdgpu_ws_layout(s->d_ws, bound).cnt : nullptr, s->stream),
            FDGPU_ERR_DEVICE);
     s->io_cnt_dirty = true;                            /* until this batch's finish is queued */
     if (!e->merges.empty() && zero_cnt && bound) {

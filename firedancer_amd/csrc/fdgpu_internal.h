@@ -123,9 +123,35 @@ hipError_t fdgpu_launch_sha512_stream(const uint8_t *d_mbuf, uint64_t m0, uint64
 hipError_t fdgpu_launch_verify_prehashed(const uint8_t *d_arena, const fdgpu_sig_desc_t *d_sigs, uint32_t n_sig,
                                          const uint32_t *d_btab, uint32_t *d_ws, int8_t *d_sig_codes, uint32_t flags,
                                          hipStream_t stream);
-/* the verify launch's queue counter for an n_sig grid in d_ws: a caller whose
-   earlier kernel on the stream zeroes it passes cnt_zeroed (no memset) */
-uint32_t  *fdgpu_verify_cnt_word(uint32_t *d_ws, uint32_t n_sig);
+/* The verify workspace of an n_sig batch, in u32 words from d_ws: the lanes'
+   words (FDGPU_WS_LANE_WORDS each, lanes = n_sig rounded up to whole blocks),
+   the fallback queue (one word per lane), 16 words of counters (the queue's
+   count, then the key cache's representative count), the key cache's hash
+   table (ht_slots, a power of two >= 2 lanes and >= 64), then key_of,
+   verdicts and representatives (one word per lane each).  A caller whose
+   earlier kernel on the stream zeroes *cnt passes cnt_zeroed to
+   fdgpu_launch_verify_sigs (no memset). */
+typedef struct {
+  uint64_t lanes, ht_slots;
+  uint32_t *queue, *cnt, *rep_cnt, *ht, *key_of, *kverd, *reps;
+  size_t bytes;
+} fdgpu_ws_layout_t;
+static inline fdgpu_ws_layout_t fdgpu_ws_layout(uint32_t *d_ws, uint64_t n_sig) {
+  fdgpu_ws_layout_t l;
+  l.lanes = (n_sig + FDGPU_BLOCK - 1) / FDGPU_BLOCK * FDGPU_BLOCK;
+  for (l.ht_slots = 64; l.ht_slots < 2 * l.lanes;) l.ht_slots <<= 1;
+  const uint64_t queue = l.lanes * FDGPU_WS_LANE_WORDS, cnt = queue + l.lanes, ht = cnt + 16, key_of = ht + l.ht_slots;
+  auto at = [d_ws](uint64_t word) { return d_ws ? d_ws + word : nullptr; };   /* NULL: only the sizes are wanted */
+  l.queue = at(queue);
+  l.cnt = at(cnt);
+  l.rep_cnt = at(cnt + 1);
+  l.ht = at(ht);
+  l.key_of = at(key_of);
+  l.kverd = at(key_of + l.lanes);
+  l.reps = at(key_of + 2 * l.lanes);
+  l.bytes = (size_t)(key_of + 3 * l.lanes) * sizeof(uint32_t);
+  return l;
+}
 /* One batch of a merged verify launch (FDGPU_FLAG_MERGE): what
    fdgpu_launch_verify_sigs takes per batch, read by each block from a table
    in pinned host memory (blockIdx.y picks the batch). */

@@ -38,23 +38,13 @@ using namespace fdgpu;
 #ifndef FDGPU_VERIFY_WAVES
 #define FDGPU_VERIFY_WAVES 2  /* waves per SIMD of the verify kernel: decode/pow chains want ~190 VGPRs */
 #endif
-/* A/B build switches.  The shipped library is built with every one at the
-   default below; fdgpu_build_info() reports them and smoke() / bench.py
-   refuse a library built otherwise (unless told it is an A/B build).
-     FDGPU_TAB_STORE_NT   non-temporal stores of the chain tables
-     FDGPU_TAB_LOAD_CPOL  cache-policy bits of the chain's LDS-DMA table loads
-     FDGPU_WS_SLOT        chain tables in a per-device pool indexed by resident
-                          block slot instead of by signature */
-#ifndef FDGPU_TAB_STORE_NT
-#define FDGPU_TAB_STORE_NT 0
-#endif
-#ifndef FDGPU_TAB_LOAD_CPOL
-#define FDGPU_TAB_LOAD_CPOL 0
-#endif
-#ifndef FDGPU_WS_SLOT
-#define FDGPU_WS_SLOT 0
-#endif
-#define FDGPU_WS_SLOTS 4096u        /* wave slots of the pool (>= the 2,048 verify waves a device keeps resident) */
+/* Build switches: FDGPU_VERIFY_WAVES, FDGPU_ATAB_WORDS and FDGPU_PHASE_STAMPS.
+   The shipped library is built with every one at its default;
+   fdgpu_build_info() reports them and smoke() / bench.py refuse a library
+   built otherwise (unless told it is an A/B build).  The slot-indexed
+   workspace pool and the table store / load cache-policy switches were
+   removed after their negative results (commit a5516cc is the
+   last that holds them). */
 
 namespace {
 
@@ -202,15 +192,7 @@ FDG_DEV void atab_store(uint32_t *wsl, uint32_t entry, const ge_cached &c) {
 #pragma unroll
   for (int i = 0; i < 40; i++) o[atab_pos(i)] = w[i];
 #pragma unroll
-  for (int q = 0; q < 10; q++) {
-#if FDGPU_TAB_STORE_NT
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = {o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
-    __builtin_nontemporal_store(v, (u32x4 *)(p + q));
-#else
-    p[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-#endif
-  }
+  for (int q = 0; q < 10; q++) p[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
 }
 FDG_DEV int sext4(uint32_t x) { return ((int)(x << 28)) >> 28; }
 
@@ -360,37 +342,6 @@ FDG_DEV uint32_t *lane_ws(uint32_t *ws, uint32_t i) {
   return ws + (size_t)i * FDGPU_WS_LANE_WORDS;
 }
 
-/* FDGPU_WS_SLOT: the slot pool follows the comb tables in the per-device
-   allocation (fdgpu_btab_bytes): a bitmap of FDGPU_WS_SLOTS bits (512 B),
-   then one 64-lane workspace per slot.  A wave claims a free slot at its
-   start and frees it at its end, so at most the device's resident verify
-   waves' tables are live, and a new wave rewrites lines an earlier wave used
-   instead of allocating fresh ones.  No wait: a wave that finds no free slot
-   (never, with more slots than resident waves) keeps its per-signature
-   workspace.  Per wave, not per block: a block-wide slot index in LDS would
-   push the block past 80 KB, and two no longer fit a CU. */
-#define WS_SLOT_NONE 0xFFFFFFFFu
-#define BTAB_WORDS ((size_t)BC_NDIG * BC_ENT * FDGPU_BCOMB_STRIDE)
-FDG_DEV uint32_t *ws_slot_bitmap(const uint32_t *btab) { return const_cast<uint32_t *>(btab) + BTAB_WORDS; }
-FDG_DEV uint32_t *ws_slot_lanes(const uint32_t *btab, uint32_t slot) {
-  return ws_slot_bitmap(btab) + FDGPU_WS_SLOTS / 32u + (size_t)slot * 64u * FDGPU_WS_LANE_WORDS;
-}
-FDG_DEV uint32_t ws_slot_claim(uint32_t *bm, uint32_t seed) {
-  constexpr uint32_t NW = FDGPU_WS_SLOTS / 32u;
-  for (uint32_t t = 0; t < 2u * NW; t++) {
-    const uint32_t w = (seed + t) % NW;
-    uint32_t v = __hip_atomic_load(bm + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (v != 0xFFFFFFFFu) {
-      const uint32_t b = (uint32_t)__builtin_ctz(~v);
-      const uint32_t old = atomicOr(bm + w, 1u << b);
-      if (!(old & (1u << b))) return w * 32u + b;
-      v = old | (1u << b);
-    }
-  }
-  return WS_SLOT_NONE;
-}
-FDG_DEV void ws_slot_release(uint32_t *bm, uint32_t slot) { atomicAnd(bm + slot / 32u, ~(1u << (slot % 32u))); }
-
 /* Output slot of lane i: signatures may be verified in an order grouped by
    SHA-512 block count (perm[i] = the signature's index in the caller's
    order); codes are always written in the caller's order. */
@@ -493,8 +444,7 @@ FDG_DEV void stage_entry(uint32_t *lds_wave, const uint32_t *tab, int e) {
   constexpr int NCH = 10;
 #pragma unroll
   for (int c = 0; c < NCH; c++)
-    __builtin_amdgcn_global_load_lds((const void *)(src + 4 * c), (lds_void_t *)(lds_wave + 256 * c), 16, 0,
-                                     FDGPU_TAB_LOAD_CPOL);
+    __builtin_amdgcn_global_load_lds((const void *)(src + 4 * c), (lds_void_t *)(lds_wave + 256 * c), 16, 0, 0);
 }
 
 /* The staged entry of a signed digit: q[0..9] = Y+X of the digit's point
@@ -562,13 +512,96 @@ FDG_DEV void hs_chain(ge_p1p1 &t, uint32_t (&ud)[5], uint32_t (&vd)[5], bool u_n
   }
 }
 
+/* ---- the stages the one-lane and the two-lane verify kernels share ---- */
+
+FDG_DEV uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
+  return v;
+}
+
+/* k = SHA-512(R || A || M) mod L; nb: the wave's largest block count */
+FDG_DEV void hram_k(uint32_t (&k)[8], const uint32_t (&Renc)[8], const uint32_t (&Aenc)[8], const uint8_t *arena,
+                    const fdgpu_sig_desc_t &d, uint32_t nb) {
+  uint64_t h[8];
+  sha512_hram(h, Renc, Aenc, arena + d.msg_off, d.msg_sz, nb);
+  uint32_t kx[16];
+#pragma unroll
+  for (int j = 0; j < 8; j++) { kx[2 * j] = bswap32((uint32_t)(h[j] >> 32)); kx[2 * j + 1] = bswap32((uint32_t)h[j]); }
+  sc_reduce512(k, kx);
+}
+
+/* Decode a point, test its order and build the table of its negative's
+   multiples at tab (a table's virtual base: tab_a / tab_r).  The verdict is
+   kverd's word: bit 0 decoded, bit 1 small order. */
+FDG_DEV uint32_t decode_neg_table(uint32_t *tab, const uint32_t (&enc)[8], bool ref_map) {
+  ge_p3 P, Pn;
+  const bool ok = ge_decode(P, enc, ref_map);
+  const bool small = ge_is_small_order_affine(P);
+  ge_p3_neg(Pn, P);
+  atab_build(tab, Pn);
+  return (ok ? 1u : 0u) | (small ? 2u : 0u);
+}
+
+/* split k; lanes that need no chain (already failed, or past the batch) run
+   no Euclid steps: k = 0 */
+FDG_DEV void hs_split_masked(hs_split_t &hs, const uint32_t (&k)[8], bool need) {
+  uint32_t ke[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) ke[j] = need ? k[j] : 0u;
+  hs_split(hs, ke);
+}
+
+/* the radix-16 digits of |u| and |v|; returns the lane's digit count (>= 1) */
+FDG_DEV uint32_t hs_digits(uint32_t (&ud)[5], uint32_t (&vd)[5], const hs_split_t &hs) {
+  uint32_t ndu = 0, ndv = 0;
+  recode16_160(ud, ndu, hs.u);
+  recode16_160(vd, ndv, hs.v);
+  return max(max(ndu, ndv), 1u);
+}
+
+/* the comb's scalar: w = v S mod L of a half-size lane, else S ([S]B for the
+   full-length path; 0 for a lane already failed) */
+FDG_DEV void comb_scalar(uint32_t (&w)[8], const hs_split_t &hs, const uint32_t (&S)[8], bool half) {
+  hs_wscalar(w, hs.v, hs.v_neg, S);
+#pragma unroll
+  for (int j = 0; j < 8; j++) w[j] = half ? w[j] : S[j];
+}
+
+/* a full-path lane leaves k's digits for fdgpu_full_kernel */
+FDG_DEV void park_full(uint32_t *park, const uint32_t (&k)[8]) {
+  uint32_t kd[KD_WORDS];
+  sc_recode16(kd, k);
+#pragma unroll
+  for (int j = 0; j < KD_WORDS; j++) park[HPARK_KD + j] = kd[j];
+  park[HPARK_CODE] = 0u;
+}
+
+/* append signature i of every lane with q_full to the fallback queue (rare):
+   one atomic per wave, ballot-compacted */
+FDG_DEV void queue_full_lanes(uint32_t *queue, uint32_t *queue_cnt, bool q_full, uint32_t i) {
+  const uint64_t m = __ballot(q_full);
+  if (m) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int leader = __ffsll((long long)m) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(queue_cnt, (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, leader, 64);
+    if (q_full) queue[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
+  }
+}
+
 /* The verify kernel of the half-size path; codes of lanes it settles are
    written here, lanes whose split failed are queued for fdgpu_full_kernel.
    The body takes its block index: the merged launch (fdgpu_verify_hs_multi_kernel)
    runs it for the batch blockIdx.y names.  PH (prehashed, the synchronous
    API's messages too large for one arena): the descriptor's msg_off holds
    the lane's SHA-512(R || A || M) state words, hashed beforehand in pieces
-   by fdgpu_sha512_stream_kernel; the product instantiations have PH false. */
+   by fdgpu_sha512_stream_kernel; the product instantiations have PH false.
+   The hash reduction, the S < L gate, the decodes with decode2's error order,
+   nb's wave maximum and the final check are written out here and again in
+   fdgpu_verify_pair_kernel: as calls to shared helpers they changed this
+   kernel's register allocation (256 VGPRs, 68 B of scratch per lane). */
 template <bool KC, bool PH = false>
 FDG_DEV void verify_hs_body(const uint8_t *__restrict__ arena, const fdgpu_sig_desc_t *__restrict__ sigs, uint32_t n_sig_arg,
                             const uint32_t *__restrict__ n_sig_dev, const uint32_t *__restrict__ btab,
@@ -587,14 +620,6 @@ FDG_DEV void verify_hs_body(const uint8_t *__restrict__ arena, const fdgpu_sig_d
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) nb = max(nb, (uint32_t)__shfl_xor((int)nb, off));
   uint32_t *wsl = lane_ws(ws, i);
-#if FDGPU_WS_SLOT
-  uint32_t w_slot = WS_SLOT_NONE;
-  if (!KC) {
-    if ((threadIdx.x & 63u) == 0) w_slot = ws_slot_claim(ws_slot_bitmap(btab), (bx * 4u + (threadIdx.x >> 6)) * 7u);
-    w_slot = __builtin_amdgcn_readfirstlane(w_slot);
-    if (w_slot != WS_SLOT_NONE) wsl = ws_slot_lanes(btab, w_slot) + (size_t)(threadIdx.x & 63u) * FDGPU_WS_LANE_WORDS;
-  }
-#endif
   uint32_t *park = wsl + FDGPU_WS_PARK * FDGPU_ATAB_WORDS;
   const uint32_t *ta = tab_a(wsl);             /* this lane's -A table */
   FDGPU_STAMP(0);
@@ -657,51 +682,27 @@ FDG_DEV void verify_hs_body(const uint8_t *__restrict__ arena, const fdgpu_sig_d
   const bool need = active && code == 0;
   /* split k (lanes already failed run no Euclid steps: k = 0) */
   hs_split_t hs;
-  {
-    uint32_t ke[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) ke[j] = need ? k[j] : 0u;
-    hs_split(hs, ke);
-  }
-  uint32_t ud[5], vd[5], ndu = 0, ndv = 0;
-  recode16_160(ud, ndu, hs.u);
-  recode16_160(vd, ndv, hs.v);
-  const uint32_t nd_lane = max(max(ndu, ndv), 1u);
+  hs_split_masked(hs, k, need);
+  uint32_t ud[5], vd[5];
+  const uint32_t nd_lane = hs_digits(ud, vd, hs);
   const bool full = need && (!hs.ok || nd_lane > HS_MAX_WIN || (flags & FDGPU_FLAG_KFULL));
   const bool half = need && !full;
   FDGPU_STAMP(5);
   /* [w]B (w = v S mod L), or [S]B for the full-length path; parked cached */
   {
     uint32_t w[8];
-    hs_wscalar(w, hs.v, hs.v_neg, S);
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = half ? w[j] : S[j];
+    comb_scalar(w, hs, S, half);
     ge_p3 WB;
     comb_sb(WB, w, btab);
     ge_cached c; ge_p3_to_cached(c, WB);
     atab_store(wsl, FDGPU_WS_SB, c);
   }
-  if (full) {
-    uint32_t kd[KD_WORDS];
-    sc_recode16(kd, k);
-#pragma unroll
-    for (int j = 0; j < KD_WORDS; j++) park[HPARK_KD + j] = kd[j];
-    park[HPARK_CODE] = 0u;
-#if FDGPU_WS_SLOT
-    /* fdgpu_full_kernel reads the lane's workspace by signature: a slot
-       lane parks a copy of its tables, [S]B and k there */
-    uint32_t *own = lane_ws(ws, i);
-    if (own != wsl)
-      for (uint32_t q = 0; q < FDGPU_WS_LANE_WORDS / 4u; q++) ((uint4 *)own)[q] = ((const uint4 *)wsl)[q];
-#endif
-  }
+  if (full) park_full(park, k);
   FDGPU_STAMP(6);
   bool eq = false;
   if (__any(half)) {
     /* the wave's digit count; every lane runs it (shorter strings lead with zeros) */
-    uint32_t nwin = half ? nd_lane : 1u;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nwin = max(nwin, (uint32_t)__shfl_xor((int)nwin, off));
+    const uint32_t nwin = wave_max_u32(half ? nd_lane : 1u);
 #pragma unroll 1
     for (uint32_t s = nwin; s < 40; s++) { shl4_5(ud); shl4_5(vd); }
     ge_p1p1 t;
@@ -725,23 +726,7 @@ FDG_DEV void verify_hs_body(const uint8_t *__restrict__ arena, const fdgpu_sig_d
   }
   FDGPU_STAMP(7);
   if (active && !full) codes[out_idx(perm, i)] = (int8_t)(code ? code : (eq ? 0 : -3));
-  {                                             /* queue the full-length lanes (rare) */
-    const uint64_t m = __ballot(full);
-    if (m) {
-      const int lane = (int)(threadIdx.x & 63u);
-      const int leader = __ffsll((long long)m) - 1;
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(queue_cnt, (uint32_t)__popcll(m));
-      base = (uint32_t)__shfl((int)base, leader, 64);
-      if (full) queue[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
-    }
-  }
-#if FDGPU_WS_SLOT
-  if (!KC && w_slot != WS_SLOT_NONE) {          /* every access of the wave to its slot has completed: free it */
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if ((threadIdx.x & 63u) == 0) ws_slot_release(ws_slot_bitmap(btab), w_slot);
-  }
-#endif
+  queue_full_lanes(queue, queue_cnt, full, i);
 }
 
 template <bool KC, bool PH = false>
@@ -880,23 +865,14 @@ fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc
   const bool active = i < n_sig;
   const bool ref_map = (flags & FDGPU_FLAG_REF_MAP) != 0;
   const fdgpu_sig_desc_t d = sigs[active ? i : n_sig - 1];
-  uint32_t nb = sha512_hram_blocks(d.msg_sz);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) nb = max(nb, (uint32_t)__shfl_xor((int)nb, off));
+  const uint32_t nb = wave_max_u32(sha512_hram_blocks(d.msg_sz));
   uint32_t *wsl = lane_ws(ws, i);             /* i < the workspace's lanes: ceil(n / 128) x 128 <= ceil(n / 256) x 256 */
-  uint32_t *park = wsl + FDGPU_WS_PARK * FDGPU_ATAB_WORDS;
+  uint32_t *tab = rl ? tab_r(wsl) : tab_a(wsl);                 /* the lane's own table */
   uint32_t Renc[8], Aenc[8];
   load32(Renc, arena + d.sig_off);
   load32(Aenc, arena + d.pub_off);
   uint32_t k[8];
-  {
-    uint64_t h[8];
-    sha512_hram(h, Renc, Aenc, arena + d.msg_off, d.msg_sz, nb);
-    uint32_t kx[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) { kx[2 * j] = bswap32((uint32_t)(h[j] >> 32)); kx[2 * j + 1] = bswap32((uint32_t)h[j]); }
-    sc_reduce512(k, kx);
-  }
+  hram_k(k, Renc, Aenc, arena, d, nb);
   uint32_t S[8];
   load32(S, arena + d.sig_off + 32);
   int code = sc_lt_L(S) ? 0 : -1;
@@ -907,13 +883,8 @@ fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc
     uint32_t enc[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) enc[j] = rl ? Renc[j] : Aenc[j];
-    ge_p3 P, Pn;
-    const bool ok = ge_decode(P, enc, ref_map);
-    const bool small = ge_is_small_order_affine(P);
-    ge_p3_neg(Pn, P);
-    atab_build(rl ? tab_r(wsl) : tab_a(wsl), Pn);
     /* both verdicts in both lanes, in decode2's order (A first) */
-    const uint32_t mine = (ok ? 1u : 0u) | (small ? 2u : 0u);
+    const uint32_t mine = decode_neg_table(tab, enc, ref_map);
     const uint32_t other = (uint32_t)__shfl_xor((int)mine, 1);
     const uint32_t av = rl ? other : mine, rv = rl ? mine : other;
     if (code == 0 && !(av & 1u)) code = ref_map ? -2 : -1;
@@ -923,23 +894,14 @@ fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc
   }
   const bool need = active && code == 0;
   hs_split_t hs;
-  {
-    uint32_t ke[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) ke[j] = need ? k[j] : 0u;
-    hs_split(hs, ke);
-  }
-  uint32_t ud[5], vd[5], ndu = 0, ndv = 0;
-  recode16_160(ud, ndu, hs.u);
-  recode16_160(vd, ndv, hs.v);
-  const uint32_t nd_lane = max(max(ndu, ndv), 1u);
+  hs_split_masked(hs, k, need);
+  uint32_t ud[5], vd[5];
+  const uint32_t nd_lane = hs_digits(ud, vd, hs);
   const bool full = need && (!hs.ok || nd_lane > HS_MAX_WIN || (flags & FDGPU_FLAG_KFULL));
   const bool half = need && !full;
   {
     uint32_t w[8];
-    hs_wscalar(w, hs.v, hs.v_neg, S);
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = half ? w[j] : S[j];
+    comb_scalar(w, hs, S, half);
     /* the A lane sums the comb's low tables, the R lane its high ones; the
        halves are exchanged and added */
     ge_p3 WB, WBo;
@@ -954,25 +916,17 @@ fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc
     ge_p3_to_cached(c, WB);
     if (!rl) atab_store(wsl, FDGPU_WS_SB, c);
   }
-  if (full && !rl) {
-    uint32_t kd[KD_WORDS];
-    sc_recode16(kd, k);
-#pragma unroll
-    for (int j = 0; j < KD_WORDS; j++) park[HPARK_KD + j] = kd[j];
-    park[HPARK_CODE] = 0u;
-  }
+  if (full && !rl) park_full(wsl + FDGPU_WS_PARK * FDGPU_ATAB_WORDS, k);
   bool eq = false;
   if (__any(half)) {
-    uint32_t nwin = half ? nd_lane : 1u;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nwin = max(nwin, (uint32_t)__shfl_xor((int)nwin, off));
+    const uint32_t nwin = wave_max_u32(half ? nd_lane : 1u);
     uint32_t dd[5];
 #pragma unroll
     for (int j = 0; j < 5; j++) dd[j] = rl ? vd[j] : ud[j];
 #pragma unroll 1
     for (uint32_t s2 = nwin; s2 < 40; s2++) shl4_5(dd);
     ge_p1p1 t;
-    hs_chain1(t, dd, rl ? hs.v_neg : hs.u_neg, nwin, rl ? tab_r(wsl) : tab_a(wsl));
+    hs_chain1(t, dd, rl ? hs.v_neg : hs.u_neg, nwin, tab);
     /* exchange the halves and add: both lanes hold [u](-A) + [v](-R) */
     ge_p3 mine, other;
     ge_p1p1_to_p3(mine, t);
@@ -1001,18 +955,7 @@ fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc
     eq = ex && fe_iszero(l1);
   }
   if (active && !full && !rl) codes[out_idx(perm, i)] = (int8_t)(code ? code : (eq ? 0 : -3));
-  {
-    const bool q_full = full && !rl;
-    const uint64_t m = __ballot(q_full);
-    if (m) {
-      const int lane = (int)(threadIdx.x & 63u);
-      const int leader = __ffsll((long long)m) - 1;
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(queue_cnt, (uint32_t)__popcll(m));
-      base = (uint32_t)__shfl((int)base, leader, 64);
-      if (q_full) queue[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
-    }
-  }
+  queue_full_lanes(queue, queue_cnt, full && !rl, i);
 }
 
 /* ---------------- key cache (FDGPU_FLAG_KCACHE) ----------------
@@ -1107,12 +1050,7 @@ fdgpu_key_table_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc_t
   const uint32_t i = reps[q];
   uint32_t Aenc[8];
   load32(Aenc, arena + sigs[i].pub_off);
-  ge_p3 P, Pn;
-  const bool a_ok = ge_decode(P, Aenc, (flags & FDGPU_FLAG_REF_MAP) != 0);
-  const bool a_small = ge_is_small_order_affine(P);
-  ge_p3_neg(Pn, P);
-  atab_build(tab_a(lane_ws(ws, i)), Pn);
-  kverd[i] = (a_ok ? 1u : 0u) | (a_small ? 2u : 0u);
+  kverd[i] = decode_neg_table(tab_a(lane_ws(ws, i)), Aenc, (flags & FDGPU_FLAG_REF_MAP) != 0);
 }
 
 /* The queued lanes of fdgpu_verify_hs_kernel: [S]B + [k](-A) with k's 64
@@ -1272,16 +1210,11 @@ __global__ void __launch_bounds__(64) fdgpu_test_hram_kernel(const uint8_t *aren
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = i < n;
   const fdgpu_sig_desc_t d = sigs[active ? i : n - 1];
-  uint32_t nb = sha512_hram_blocks(d.msg_sz);
-  for (int off = 32; off > 0; off >>= 1) nb = max(nb, (uint32_t)__shfl_xor((int)nb, off));
-  uint32_t R[8], A[8];
+  const uint32_t nb = wave_max_u32(sha512_hram_blocks(d.msg_sz));
+  uint32_t R[8], A[8], k[8];
   load32(R, arena + d.sig_off);
   load32(A, arena + d.pub_off);
-  uint64_t h[8];
-  sha512_hram(h, R, A, arena + d.msg_off, d.msg_sz, nb);
-  uint32_t kx[16], k[8];
-  for (int j = 0; j < 8; j++) { kx[2 * j] = bswap32((uint32_t)(h[j] >> 32)); kx[2 * j + 1] = bswap32((uint32_t)h[j]); }
-  sc_reduce512(k, kx);
+  hram_k(k, R, A, arena, d, nb);
   if (!active) return;
   for (int j = 0; j < 8; j++) out[8 * i + j] = k[j];
 }
@@ -1783,23 +1716,17 @@ char const *fdgpu_kernel_path(void) { return "halfsize: fdgpu_verify_hs_kernel +
 /* every compile-time switch of the kernels, as JSON members; the return
    value is 1 iff each is at the shipped default (fdgpu_build_info) */
 int fdgpu_kernel_build_info(char *buf, size_t n) {
-  snprintf(buf, n, "\"verify_waves\":%d,\"atab_words\":%u,\"tab_store_nt\":%d,\"tab_load_cpol\":%d,\"ws_slot\":%d,"
-           "\"phase_stamps\":%d", (int)FDGPU_VERIFY_WAVES, (unsigned)FDGPU_ATAB_WORDS, (int)FDGPU_TAB_STORE_NT,
-           (int)FDGPU_TAB_LOAD_CPOL, (int)FDGPU_WS_SLOT, (int)FDGPU_PHASE_STAMPS);
-  return FDGPU_VERIFY_WAVES == 2 && FDGPU_ATAB_WORDS == 40u && FDGPU_TAB_STORE_NT == 0 && FDGPU_TAB_LOAD_CPOL == 0 &&
-         FDGPU_WS_SLOT == 0 && FDGPU_PHASE_STAMPS == 0;
+  snprintf(buf, n, "\"verify_waves\":%d,\"atab_words\":%u,\"phase_stamps\":%d", (int)FDGPU_VERIFY_WAVES,
+           (unsigned)FDGPU_ATAB_WORDS, (int)FDGPU_PHASE_STAMPS);
+  return FDGPU_VERIFY_WAVES == 2 && FDGPU_ATAB_WORDS == 40u && FDGPU_PHASE_STAMPS == 0;
 }
 
-size_t fdgpu_btab_bytes(void) {
-  return (BTAB_WORDS + (FDGPU_WS_SLOT ? FDGPU_WS_SLOTS / 32u + (size_t)FDGPU_WS_SLOTS * 64u * FDGPU_WS_LANE_WORDS : 0)) *
-         sizeof(uint32_t);
-}
+size_t fdgpu_btab_bytes(void) { return (size_t)BC_NDIG * BC_ENT * FDGPU_BCOMB_STRIDE * sizeof(uint32_t); }
 
 hipError_t fdgpu_btab_build(uint32_t *d_btab, hipStream_t stream) {
   uint32_t *bases = nullptr, *scratch = nullptr;
   const uint32_t lanes = BC_NDIG * BC_CHUNKS;
-  hipError_t e = FDGPU_WS_SLOT ? hipMemsetAsync(d_btab + BTAB_WORDS, 0, FDGPU_WS_SLOTS / 8u, stream) : hipSuccess;
-  if (e == hipSuccess) e = hipMalloc((void **)&bases, BC_NDIG * 40 * sizeof(uint32_t));
+  hipError_t e = hipMalloc((void **)&bases, BC_NDIG * 40 * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc((void **)&scratch, (size_t)lanes * FDGPU_BCOMB_CHUNK * 10 * sizeof(uint32_t));
   if (e == hipSuccess) {
     hipLaunchKernelGGL(fdgpu_bcomb_base_kernel, dim3(1), dim3(64), 0, stream, bases);
@@ -1819,19 +1746,7 @@ hipError_t fdgpu_verify_occupancy(int *blocks_per_cu) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fdgpu_verify_hs_kernel<false>, FDGPU_BLOCK, 0);
 }
 
-/* workspace: per-lane words, the fallback queue, its counter and the key
-   cache's representative count (16 words), then the key cache's hash table,
-   key_of, verdicts and representative list */
-static uint64_t kc_ht_slots(uint64_t lanes) {       /* power of two >= 2 lanes */
-  uint64_t h = 64;
-  while (h < 2 * lanes) h <<= 1;
-  return h;
-}
-
-size_t fdgpu_ws_bytes(uint64_t n_sig) {
-  const uint64_t grid = (n_sig + FDGPU_BLOCK - 1) / FDGPU_BLOCK, lanes = grid * FDGPU_BLOCK;
-  return (size_t)(lanes * FDGPU_WS_LANE_WORDS + lanes + 16 + kc_ht_slots(lanes) + 3 * lanes) * sizeof(uint32_t);
-}
+size_t fdgpu_ws_bytes(uint64_t n_sig) { return fdgpu_ws_layout(nullptr, n_sig).bytes; }
 
 hipError_t fdgpu_launch_verify_sigs(const uint8_t *d_arena, const fdgpu_sig_desc_t *d_sigs, uint32_t n_sig,
                                     const uint32_t *d_perm, const uint32_t *d_btab, uint32_t *d_ws,
@@ -1839,9 +1754,8 @@ hipError_t fdgpu_launch_verify_sigs(const uint8_t *d_arena, const fdgpu_sig_desc
                                     uint32_t resident_blocks, uint64_t kc_seed, int cnt_zeroed) {
   if (!n_sig) return hipSuccess;
   const uint32_t grid = (n_sig + FDGPU_BLOCK - 1) / FDGPU_BLOCK;
-  const size_t lanes = (size_t)grid * FDGPU_BLOCK;
-  uint32_t *queue = d_ws + lanes * FDGPU_WS_LANE_WORDS, *cnt = queue + lanes;
-  hipError_t e = cnt_zeroed ? hipSuccess : hipMemsetAsync(cnt, 0, sizeof(uint32_t), stream);
+  const fdgpu_ws_layout_t l = fdgpu_ws_layout(d_ws, n_sig);
+  hipError_t e = cnt_zeroed ? hipSuccess : hipMemsetAsync(l.cnt, 0, sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
   /* the queued full-length lanes get as many blocks as the batch's grid could
      keep resident (all of them, up to every wave slot of the GPU: the
@@ -1854,30 +1768,28 @@ hipError_t fdgpu_launch_verify_sigs(const uint8_t *d_arena, const fdgpu_sig_desc
   if (slow_blocks > slow_cap) slow_blocks = slow_cap;
   const uint32_t *key_of = nullptr;
   if (flags & FDGPU_FLAG_KCACHE) {
-    const uint64_t hts = kc_ht_slots(lanes);
-    uint32_t *ht = cnt + 16, *kof = ht + hts, *kverd = kof + lanes, *reps = kverd + lanes, *rep_cnt = cnt + 1;
-    e = hipMemsetAsync(ht, 0xff, hts * sizeof(uint32_t), stream);
-    if (e == hipSuccess) e = hipMemsetAsync(rep_cnt, 0, sizeof(uint32_t), stream);
+    e = hipMemsetAsync(l.ht, 0xff, l.ht_slots * sizeof(uint32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(l.rep_cnt, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fdgpu_key_dedup_kernel, dim3((n_sig + 255) / 256), dim3(256), 0, stream, d_arena, d_sigs, n_sig,
-                       d_n_sig, ht, (uint32_t)(hts - 1), kof, reps, rep_cnt, kc_seed);
-    hipLaunchKernelGGL(fdgpu_key_table_kernel, dim3(grid), dim3(FDGPU_BLOCK), 0, stream, d_arena, d_sigs, d_ws, reps,
-                       rep_cnt, kverd, flags);
+                       d_n_sig, l.ht, (uint32_t)(l.ht_slots - 1), l.key_of, l.reps, l.rep_cnt, kc_seed);
+    hipLaunchKernelGGL(fdgpu_key_table_kernel, dim3(grid), dim3(FDGPU_BLOCK), 0, stream, d_arena, d_sigs, d_ws, l.reps,
+                       l.rep_cnt, l.kverd, flags);
     hipLaunchKernelGGL(fdgpu_verify_hs_kernel<true>, dim3(grid), dim3(FDGPU_BLOCK), 0, stream, d_arena, d_sigs, n_sig,
-                       d_n_sig, d_btab, d_ws, d_perm, d_sig_codes, queue, cnt, flags, kof, kverd);
-    key_of = kof;
+                       d_n_sig, d_btab, d_ws, d_perm, d_sig_codes, l.queue, l.cnt, flags, l.key_of, l.kverd);
+    key_of = l.key_of;
   } else if (flags & FDGPU_FLAG_KPAIR) {
     const uint32_t pgrid = (2u * n_sig + FDGPU_BLOCK - 1) / FDGPU_BLOCK;     /* two lanes per signature */
     hipLaunchKernelGGL(fdgpu_verify_pair_kernel, dim3(pgrid), dim3(FDGPU_BLOCK),
                        (flags & FDGPU_FLAG_KSPREAD) ? FDGPU_SPREAD_LDS_PAIR : 0, stream, d_arena, d_sigs, n_sig,
-                       d_n_sig, d_btab, d_ws, d_perm, d_sig_codes, queue, cnt, flags);
+                       d_n_sig, d_btab, d_ws, d_perm, d_sig_codes, l.queue, l.cnt, flags);
   } else {
     hipLaunchKernelGGL(fdgpu_verify_hs_kernel<false>, dim3(grid), dim3(FDGPU_BLOCK),
                        (flags & FDGPU_FLAG_KSPREAD) ? FDGPU_SPREAD_LDS : 0, stream, d_arena, d_sigs, n_sig,
-                       d_n_sig, d_btab, d_ws, d_perm, d_sig_codes, queue, cnt, flags, nullptr, nullptr);
+                       d_n_sig, d_btab, d_ws, d_perm, d_sig_codes, l.queue, l.cnt, flags, nullptr, nullptr);
   }
   hipLaunchKernelGGL(fdgpu_full_kernel, dim3(slow_blocks), dim3(FDGPU_BLOCK), 0, stream, d_ws, d_perm, d_sig_codes,
-                     queue, cnt, slow_blocks * FDGPU_BLOCK, key_of);
+                     l.queue, l.cnt, slow_blocks * FDGPU_BLOCK, key_of);
   return hipGetLastError();
 }
 
@@ -1897,15 +1809,14 @@ hipError_t fdgpu_launch_verify_prehashed(const uint8_t *d_arena, const fdgpu_sig
                                          hipStream_t stream) {
   if (!n_sig) return hipSuccess;
   const uint32_t grid = (n_sig + FDGPU_BLOCK - 1) / FDGPU_BLOCK;
-  const size_t lanes = (size_t)grid * FDGPU_BLOCK;
-  uint32_t *queue = d_ws + lanes * FDGPU_WS_LANE_WORDS, *cnt = queue + lanes;
-  hipError_t e = hipMemsetAsync(cnt, 0, sizeof(uint32_t), stream);
+  const fdgpu_ws_layout_t l = fdgpu_ws_layout(d_ws, n_sig);
+  hipError_t e = hipMemsetAsync(l.cnt, 0, sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((fdgpu_verify_hs_kernel<false, true>), dim3(grid), dim3(FDGPU_BLOCK), 0, stream, d_arena, d_sigs,
-                     n_sig, nullptr, d_btab, d_ws, nullptr, d_sig_codes, queue, cnt, flags & FDGPU_FLAG_REF_MAP,
+                     n_sig, nullptr, d_btab, d_ws, nullptr, d_sig_codes, l.queue, l.cnt, flags & FDGPU_FLAG_REF_MAP,
                      nullptr, nullptr);
-  hipLaunchKernelGGL(fdgpu_full_kernel, dim3(1), dim3(FDGPU_BLOCK), 0, stream, d_ws, nullptr, d_sig_codes, queue, cnt,
-                     FDGPU_BLOCK, nullptr);
+  hipLaunchKernelGGL(fdgpu_full_kernel, dim3(1), dim3(FDGPU_BLOCK), 0, stream, d_ws, nullptr, d_sig_codes, l.queue,
+                     l.cnt, FDGPU_BLOCK, nullptr);
   return hipGetLastError();
 }
 
@@ -1915,11 +1826,6 @@ hipError_t fdgpu_launch_verify_multi(const fdgpu_mbatch_t *mb, uint32_t nb, uint
   hipLaunchKernelGGL(fdgpu_verify_hs_multi_kernel, dim3(grid_max, nb), dim3(FDGPU_BLOCK), 0, stream, mb, d_btab, flags);
   hipLaunchKernelGGL(fdgpu_full_multi_kernel, dim3(slow_max ? slow_max : 1, nb), dim3(FDGPU_BLOCK), 0, stream, mb);
   return hipGetLastError();
-}
-
-uint32_t *fdgpu_verify_cnt_word(uint32_t *d_ws, uint32_t n_sig) {
-  const size_t lanes = (size_t)((n_sig + FDGPU_BLOCK - 1) / FDGPU_BLOCK) * FDGPU_BLOCK;
-  return d_ws + lanes * FDGPU_WS_LANE_WORDS + lanes;
 }
 
 hipError_t fdgpu_launch_combine(const fdgpu_txn_desc_t *d_txns, uint32_t n_txn, const int8_t *d_sig_codes,

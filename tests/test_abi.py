@@ -104,8 +104,10 @@ def test_shipped_library_is_product_build():
     reported as not a product build (so the guard is not vacuous)."""
     info = _lib.build_info()
     assert info["product"] == 1, info
-    assert (info["verify_waves"], info["atab_words"], info["tab_store_nt"], info["tab_load_cpol"], info["ws_slot"],
-            info["phase_stamps"], info["debug_drop_flag"]) == (2, 40, 0, 0, 0, 0, 0), info
+    assert (info["verify_waves"], info["atab_words"], info["phase_stamps"], info["debug_drop_flag"]) == (2, 40, 0, 0), info
+    # exactly the reported switches: one that reappears without being checked here fails
+    assert set(info) == {"verify_waves", "atab_words", "phase_stamps", "copy_threads", "debug_drop_flag",
+                         "debug_fail_merge", "product"}, info
     assert _lib.require_product_build() == info
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     probe = ("import json, sys; sys.path.insert(0, {r!r}); from firedancer_amd import _lib; "
@@ -125,6 +127,22 @@ def test_shipped_library_is_product_build():
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".h", ".cpp")):
             assert "FDGPU_DIAG_" not in open(os.path.join(csrc, f)).read(), f
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 8192, 1000000])
+def test_ws_bytes_is_the_documented_layout(n):
+    """fdgpu_ws_bytes: per-lane words, the fallback queue, 16 counter words,
+    the key cache's hash table (a power of two >= 2 lanes, at least 64), then
+    key_of, verdicts and representatives, for n rounded up to 256-lane blocks."""
+    L = _lib.lib()
+    L.fdgpu_ws_bytes.restype = ctypes.c_size_t
+    L.fdgpu_ws_bytes.argtypes = [ctypes.c_uint64]
+    lane_words = 18 * 40                    # FDGPU_WS_ENTRIES x FDGPU_ATAB_WORDS
+    lanes = (n + 255) // 256 * 256
+    ht = 64
+    while ht < 2 * lanes:
+        ht *= 2
+    assert L.fdgpu_ws_bytes(n) == 4 * (lanes * lane_words + lanes + 16 + ht + 3 * lanes)
 
 
 def test_stamps_variant_builds():
