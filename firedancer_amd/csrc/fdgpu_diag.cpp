@@ -1,0 +1,124 @@
+/* fdgpu_diag.cpp -- the fdgpu_debug_* diagnostics that run the kernels' building blocks (field, decode, SHA-512,
+   scalar) on caller data, for the parity tests.  Synchronous, on the engine's compute stream. */
+#include "fdgpu_engine.h"
+
+using namespace fdgpu;
+
+/* n elements of the buffer's type, and a cache line to spare */
+#define DALLOC(buf, n) do { if ((buf).alloc((size_t)(n) * sizeof(*(buf).p) + 64) != hipSuccess) { \
+  set_err("alloc"); return FDGPU_ERR_DEVICE; } } while (0)
+
+static int debug_msgs(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *txns, uint64_t n,
+                      uint8_t *out, int hram) {
+  if (!e || !n) return FDGPU_ERR_INVAL;
+  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
+  std::vector<fdgpu_sig_desc_t> d(n);
+  for (uint64_t i = 0; i < n; i++) {
+    if ((uint64_t)txns[i].msg_off + txns[i].msg_sz > arena_sz ||
+        (hram && ((uint64_t)txns[i].sig_off + 64 > arena_sz || (uint64_t)txns[i].pub_off + 32 > arena_sz))) {
+      set_err("descriptor out of bounds"); return FDGPU_ERR_INVAL;
+    }
+    d[i].msg_off = txns[i].msg_off; d[i].msg_sz = txns[i].msg_sz;
+    d[i].sig_off = txns[i].sig_off; d[i].pub_off = txns[i].pub_off;
+  }
+  DevBuf<uint8_t> da;
+  DevBuf<fdgpu_sig_desc_t> dd;
+  DevBuf<uint32_t> dout;
+  DALLOC(da, arena_sz + FDGPU_ARENA_SLACK);
+  DALLOC(dd, n);
+  DALLOC(dout, n * 16);
+  HIPCHK(hipMemset(da, 0, arena_sz + FDGPU_ARENA_SLACK), FDGPU_ERR_DEVICE);
+  if (arena_sz) HIPCHK(hipMemcpy(da, arena, arena_sz, hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(dd, d.data(), n * sizeof(fdgpu_sig_desc_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
+  if (hram)
+    HIPCHK(fdgpu_launch_test_hram(da, dd, (uint32_t)n, dout, e->compute), FDGPU_ERR_DEVICE);
+  else
+    HIPCHK(fdgpu_launch_test_sha512(da, dd, (uint32_t)n, dout, e->compute), FDGPU_ERR_DEVICE);
+  HIPCHK(hipStreamSynchronize(e->compute), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(out, dout, n * (hram ? 32 : 64), hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
+  return FDGPU_OK;
+}
+
+/* n elements of in_words u32 each through one of the test kernels, out_words u32 each back */
+template <class Launch>
+static int debug_map(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint64_t in_words, uint64_t out_words,
+                     uint8_t *out, Launch launch) {
+  if (!e || !n) return FDGPU_ERR_INVAL;
+  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
+  DevBuf<uint32_t> din, dout;
+  DALLOC(din, n * in_words);
+  DALLOC(dout, n * out_words);
+  HIPCHK(hipMemcpy(din, in, n * in_words * 4, hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
+  HIPCHK(launch(din.p, dout.p, (uint32_t)n, e->compute), FDGPU_ERR_DEVICE);
+  HIPCHK(hipStreamSynchronize(e->compute), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(out, dout, n * out_words * 4, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
+  return FDGPU_OK;
+}
+
+extern "C" {
+
+int fdgpu_debug_fe_ops(fdgpu_engine_t *e, uint8_t const *ab, uint64_t n, uint8_t *out) {
+  return debug_map(e, ab, n, 16, 64, out, fdgpu_launch_test_fe);
+}
+
+int fdgpu_debug_decode(fdgpu_engine_t *e, uint8_t const *enc, uint64_t n, int ref_mapping, uint8_t *out) {
+  const uint32_t flags = ref_mapping ? FDGPU_FLAG_REF_MAP : 0u;
+  return debug_map(e, enc, n, 8, 18, out, [flags](const uint32_t *i, uint32_t *o, uint32_t k, hipStream_t st) {
+    return fdgpu_launch_test_decode(i, o, k, flags, st);
+  });
+}
+
+int fdgpu_debug_sha512(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *msgs,
+                       uint64_t n, uint8_t *out) {
+  return debug_msgs(e, arena, arena_sz, msgs, n, out, 0);
+}
+
+int fdgpu_debug_hram(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *txns,
+                     uint64_t n, uint8_t *out) {
+  return debug_msgs(e, arena, arena_sz, txns, n, out, 1);
+}
+
+int fdgpu_debug_sc_reduce(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint8_t *out) {
+  return debug_map(e, in, n, 16, 8, out, fdgpu_launch_test_sc_reduce);
+}
+
+int fdgpu_debug_hs_split(fdgpu_engine_t *e, uint8_t const *k, uint64_t n, uint8_t *out) {
+  return debug_map(e, k, n, 8, 16, out, fdgpu_launch_test_hs_split);
+}
+
+int fdgpu_debug_sig_codes(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *txns,
+                          uint64_t txn_cnt, int8_t *sig_codes) {
+  if (!e) return FDGPU_ERR_INVAL;
+  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
+  uint64_t total = 0;
+  for (uint64_t t = 0; t < txn_cnt; t++) total += (txns[t].sig_cnt >= 1 && txns[t].sig_cnt <= 16) ? txns[t].sig_cnt : 0;
+  std::vector<fdgpu_sig_desc_t> sd(total + 1);
+  std::vector<fdgpu_txn_desc_t> td(txn_cnt + 1);
+  std::vector<uint32_t> pm(total + 1);
+  uint32_t *perm = bucket(e) ? pm.data() : nullptr;
+  const int64_t ns = expand(arena_sz, txns, txn_cnt, total, sd.data(), td.data(), perm);
+  if (ns < 0) return FDGPU_ERR_INVAL;
+  if (!ns) return FDGPU_OK;
+  DevBuf<uint8_t> da;
+  DevBuf<fdgpu_sig_desc_t> dd;
+  DevBuf<uint32_t> dp;
+  DevBuf<int8_t> dc;
+  DALLOC(da, arena_sz + FDGPU_ARENA_SLACK);
+  DALLOC(dd, ns);
+  DALLOC(dp, ns);
+  DALLOC(dc, ns);
+  HIPCHK(hipMemset(da, 0, arena_sz + FDGPU_ARENA_SLACK), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(da, arena, arena_sz, hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(dd, sd.data(), ns * sizeof(fdgpu_sig_desc_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
+  if (perm) HIPCHK(hipMemcpy(dp, perm, ns * sizeof(uint32_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
+  const uint32_t flags = kflags(e);
+  if ((uint64_t)ns > e->ws_sig) { int rc = ensure_ws(e, (uint64_t)ns); if (rc) return rc; }
+  HIPCHK(fdgpu_launch_verify_sigs(da, dd, (uint32_t)ns, perm ? dp.p : nullptr, e->d_btab, e->d_ws, dc, flags,
+                                  e->compute, nullptr, e->resident_blocks, e->kc_seed),
+         FDGPU_ERR_DEVICE);
+  HIPCHK(hipStreamSynchronize(e->compute), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(sig_codes, dc, ns, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
+  return FDGPU_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 /* fdgpu_internal.h -- declarations shared by the kernels (fdgpu_kernels.hip)
-   and the host engine (fdgpu_engine.cpp).  Not part of the public C ABI. */
+   and the host engine (fdgpu_engine.h).  Not part of the public C ABI. */
 #pragma once
 
 #include <hip/hip_runtime_api.h>

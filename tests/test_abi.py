@@ -34,6 +34,18 @@ def test_dynamic_symbol_table_lists_exports():
         assert n in syms, n
 
 
+def test_engine_internals_are_not_exported():
+    """The engine's units share their internals through namespace fdgpu
+    (csrc/fdgpu_engine.h, hidden visibility): none of them is a dynamic
+    symbol, so nothing that links the library can interpose one."""
+    out = subprocess.run(["nm", "-D", "-C", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True,
+                         check=True).stdout
+    names = [ln.split(None, 2)[2] for ln in out.splitlines() if len(ln.split(None, 2)) == 3]
+    assert len(names) > 50, out[:500]           # the table was read
+    leaked = [n for n in names if "fdgpu::" in n]
+    assert not leaked, leaked
+
+
 def test_header_is_plain_c():
     """The boundary header compiles as C11 with no HIP/torch includes."""
     src = f'#include "{_lib.HEADER_PATH}"\nint main(void){{ fdgpu_txn_t t; (void)t; return FD_ED25519_ERR_MSG + 3; }}\n'

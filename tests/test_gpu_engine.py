@@ -181,7 +181,7 @@ def test_stamps_variant_codes(tmp_path):
 
 def test_registered_arena_slack_left_unwritten(oracle):
     """A registered arena is DMA'd as it is and the slack past it on the
-    device is not zeroed (fdgpu_engine.cpp submit_slot): the SHA block loads
+    device is not zeroed (fdgpu_ring.cpp submit_slot): the SHA block loads
     mask every byte past the message.  The slot's device arena first holds a
     longer batch of 0xA5 bytes, then a registered arena that ends exactly at
     its last message's last byte: every code equals the oracle's."""

@@ -273,7 +273,7 @@ def test_async_ring(engine):
 
 def test_threaded_staging_large_arena(engine, oracle):
     """Arenas >= 4 MB are staged by 4 host threads, each queuing its part's
-    upload (fdgpu_engine.cpp stage_arena); sizes straddle the part rounding."""
+    upload (fdgpu_ring.cpp stage_arena); sizes straddle the part rounding."""
     arena, txns, _ = workload.cfg1(24000, seed=0x5151)
     exp = oracle.verify_txns(arena, txns, nthreads=8)
     dev = engine.upload(arena, txns)

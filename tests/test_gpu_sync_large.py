@@ -81,7 +81,7 @@ def test_sync_api_message_beyond_arena_gets_reference_code():
 def test_sync_arena_override_is_bounded():
     """The override only lowers the limit (values below 1 KiB or above the
     32-bit arena are ignored): checked on the source, no GPU needed."""
-    src = open(os.path.join(REPO, "firedancer_amd", "csrc", "fdgpu_engine.cpp")).read()
+    src = open(os.path.join(REPO, "firedancer_amd", "csrc", "fdgpu_sync.cpp")).read()
     assert 'getenv("FDGPU_SYNC_ARENA_MAX")' in src
     assert "m >= 1024 && m < SYNC_ARENA_LIMIT" in src
     assert "sync_run_prehashed" in src and "call too large" not in src

@@ -3,9 +3,10 @@
    random transaction batches with and without the block-count grouping, and
    fails the same way on out-of-bounds descriptors and max_sig overflows.
    Built and run by tests/test_expand_par.py (no GPU needed):
-     hipcc -O2 -std=c++17 -x hip tools/expand_check.cpp -o build/expand_check \
-           -L firedancer_amd -l:libfd_ed25519_gpu.so -Wl,-rpath,$PWD/firedancer_amd */
-#include "../firedancer_amd/csrc/fdgpu_engine.cpp"
+     hipcc -O2 -std=c++17 -x hip tools/expand_check.cpp -o build/expand_check
+   It compiles the engine's expansion unit alone (no HIP call in it, nothing
+   to link); the error text is the engine's thread-local fdgpu::g_err. */
+#include "../firedancer_amd/csrc/fdgpu_expand.cpp"
 
 #include <random>
 
