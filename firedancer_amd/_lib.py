@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FDGPU_LIB overrides the library path (A/B builds of kernel variants in one tree).
 LIB_PATH = os.environ.get("FDGPU_LIB") or os.path.join(_HERE, "libfd_ed25519_gpu.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_ed25519_gpu.h")
+SHRED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_shred_gpu.h")
 
 _LIB = None
 
@@ -136,6 +137,18 @@ def lib():
     L.fdgpu_sync_stats.restype = None
     L.fdgpu_sync_errors.argtypes = []
     L.fdgpu_sync_errors.restype = c.c_uint64
+    # include/fd_shred_gpu.h
+    L.fdgpu_submit_shreds.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint16]
+    L.fdgpu_submit_shreds.restype = c.c_int64
+    L.fdgpu_poll_shreds.argtypes = [vp, c.c_int64, vp, vp, c.c_int]
+    L.fdgpu_poll_shreds.restype = c.c_int
+    L.fdgpu_debug_sha256.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, vp]
+    L.fdgpu_debug_sha256.restype = c.c_int
+    L.fdgpu_debug_shred_roots.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint16, vp, vp]
+    L.fdgpu_debug_shred_roots.restype = c.c_int
+    L.fdgpu_debug_shred_time.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint16, c.c_int,
+                                         c.POINTER(c.c_double), c.POINTER(c.c_double)]
+    L.fdgpu_debug_shred_time.restype = c.c_int
     for fn in ("fdgpu_debug_fe_ops", "fdgpu_debug_decode", "fdgpu_debug_sha512", "fdgpu_debug_hram",
                "fdgpu_debug_sc_reduce", "fdgpu_debug_hs_split", "fdgpu_debug_sig_codes"):
         getattr(L, fn).restype = c.c_int
@@ -143,10 +156,10 @@ def lib():
     return L
 
 
-def header_functions():
-    """Names of the functions declared by include/fd_ed25519_gpu.h."""
+def header_functions(path=None):
+    """Names of the functions declared by include/fd_ed25519_gpu.h (or the header at path)."""
     import re
-    text = open(HEADER_PATH).read()
+    text = open(path or HEADER_PATH).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     names = re.findall(r"^[A-Za-z_][\w \t\*]*?\b(fd\w+)\s*\(", text, flags=re.M)
     return sorted(set(n for n in names if not n.startswith("FD_")))

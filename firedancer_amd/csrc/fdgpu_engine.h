@@ -1,8 +1,8 @@
 /* fdgpu_engine.h -- what the host engine's units share (fdgpu_engine.cpp, fdgpu_ring.cpp, fdgpu_frags.cpp,
-   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp): the error text, the environment switches,
+   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp, fdgpu_shreds.cpp): the error text, the environment switches,
    the owners of HIP memory, the ring's slot and the engine, the host-side buffer layouts, and the few internals more
-   than one unit calls.  Everything here has hidden visibility: the exported C ABI is include/fd_ed25519_gpu.h and
-   nothing else (tests/test_abi.py).  The kernels do not include this file. */
+   than one unit calls.  Everything here has hidden visibility: the exported C ABI is include/fd_ed25519_gpu.h and its
+   extension include/fd_shred_gpu.h, nothing else (tests/test_abi.py).  The kernels do not include this file. */
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/fd_ed25519_gpu.h"
+#include "../../include/fd_shred_gpu.h"
 #include "fdgpu_internal.h"
 #include "fdt_parse.h"
 
@@ -139,6 +140,7 @@ enum class Batch : uint8_t {
   Ring,     /* fdgpu_submit / fdgpu_stage_submit: codes in h_codes */
   Frag,     /* fdgpu_submit_frags: [codes][trailers] in h_tr */
   FragIo,   /* fdgpu_submit_frags_io: io_results() in h_tr */
+  Shred,    /* fdgpu_submit_shreds: [codes, padded to 64][roots] in h_shres */
 };
 
 struct Slot {
@@ -187,6 +189,11 @@ struct Slot {
                                                  engines, parsed and verified in place (the batch arena) */
   uint64_t mirror_cap = 0;
   uint8_t *d_trh = nullptr;                   /* h_tr's device-side address (results written in place) */
+  /* shred batches (fdgpu_submit_shreds), allocated on the slot's first one for max_txn shreds: the records, the
+     ingest's signature count, and the results [codes, padded to 64][32-B roots] with their pinned read-back */
+  HostBuf<fdgpu_shred_t> h_sh; DevBuf<fdgpu_shred_t> d_sh;
+  DevBuf<uint32_t> d_sh_cnt;
+  DevBuf<uint8_t> d_shres; HostBuf<uint8_t> h_shres;
   /* FDGPU_FLAG_MERGE: the batch's gather + parse are queued and its verify waits to be merged with the other batches
      ready (merge_kick), which then queues the rest of the batch behind it */
   hipEvent_t parsed = nullptr;
@@ -278,6 +285,9 @@ uint64_t stage_arena(fdgpu_engine_t *e, Slot *s, uint8_t const *arena, uint64_t 
 int slot_signal(fdgpu_engine_t *e, Slot *s);
 int64_t slot_publish(fdgpu_engine_t *e, Slot *s, Batch kind, uint64_t txn_cnt, uint64_t tr_sz, uint64_t tr_base,
                      bool signal_deferred = false);
+/* the poll of every batch kind: what the kind does not produce stays unwritten */
+int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking, bool keep, uint8_t *trailers = nullptr,
+              uint64_t *tags = nullptr, uint16_t *out_szs = nullptr, uint8_t *roots = nullptr);
 
 /* fdgpu_frags.cpp */
 int merge_kick(fdgpu_engine_t *e, bool force);

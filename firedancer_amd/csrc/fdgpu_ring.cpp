@@ -167,8 +167,12 @@ int64_t submit_slot(fdgpu_engine_t *e, Slot *s, uint64_t arena_sz, fdgpu_txn_t c
   return slot_publish(e, s, Batch::Ring, txn_cnt, 0, 0);
 }
 
-int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking, bool keep,
-              uint8_t *trailers = nullptr, uint64_t *tags = nullptr, uint16_t *out_szs = nullptr) {
+}  // namespace
+
+namespace fdgpu {
+
+int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking, bool keep, uint8_t *trailers,
+              uint64_t *tags, uint16_t *out_szs, uint8_t *roots) {
   if (!e) return FDGPU_ERR_INVAL;
   /* a batch still on the device is answered without the ring lock: the caller owns its ticket's slot until a poll
      returns it done, so the slot's ticket and completion word are stable here; the runtime check below (every 256th
@@ -242,13 +246,17 @@ int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking
       if (out_szs && n) memcpy(out_szs, s->h_tr + r.sizes, n * 2);
       break;
     }
+    case Batch::Shred:
+      if (txn_codes && n) memcpy(txn_codes, s->h_shres, n);
+      if (roots && n) memcpy(roots, s->h_shres + s->tr_base, n * 32);
+      break;
   }
   if (keep) st_rlx(s->held, true);
   else st_rlx(s->ticket, (int64_t)-1);
   return FDGPU_OK;
 }
 
-}  // namespace
+}  // namespace fdgpu
 
 extern "C" {
 

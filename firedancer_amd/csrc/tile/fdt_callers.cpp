@@ -9,7 +9,10 @@
      shreds   fd_fec_resolver.c:438 checks each new FEC set's merkle root
               with fd_ed25519_verify(root, 32, sig, leader_pubkey);
               fdgpu_fec_roots_verify verifies many roots in one batch
-              (32-byte messages, single signatures).
+              (32-byte messages, single signatures);
+              fdgpu_shreds_verify starts from the raw shreds: the checks
+              before the signature and the SHA-256 Merkle root on the host
+              (fdt_shred.h), then the same batched verify.
 
    Both cut the work into batches within the verifier's limits, keep up to
    two batches in flight (the next one is staged while the GPU runs the
@@ -17,9 +20,12 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
+#include <thread>
 #include <vector>
 
 #include "../../../include/fd_verify_tile.h"
+#include "../fdt_shred.h"
 
 namespace {
 
@@ -142,6 +148,78 @@ int fdgpu_fec_roots_verify(fdgpu_verifier_t v, const uint8_t *roots, const uint8
     const uint32_t base = (uint32_t)c->arena.size();
     c->arena.insert(c->arena.end(), sigs + 64 * i, sigs + 64 * i + 64);
     const uint8_t *pk = pubkeys + (shared_pubkey ? 0 : 32 * i);
+    c->arena.insert(c->arena.end(), pk, pk + 32);
+    c->arena.insert(c->arena.end(), roots + 32 * i, roots + 32 * i + 32);
+    fdgpu_txn_t d;
+    d.sig_off = base;
+    d.pub_off = base + 64;
+    d.msg_off = base + 96;
+    d.msg_sz = 32;
+    d.sig_cnt = 1;
+    c->txns.push_back(d);
+    c->items.push_back(i);
+  }
+  if (!r) r = p.submit(*c);
+  if (!r) r = p.finish();
+  return r;
+}
+
+int fdt_shred_check(const uint8_t *buf, uint64_t sz, uint16_t expected_version, fdt_shred_chk_t *out) {
+  fdt_shred_chk_t tmp;
+  const int ok = fdt_shred_check_core(buf, sz, expected_version, &tmp);
+  if (ok && out) *out = tmp;
+  return ok;
+}
+
+void fdt_shred_root(const uint8_t *buf, const fdt_shred_chk_t *chk, uint8_t *root) { fdt_shred_root_core(buf, chk, root); }
+
+void fdt_sha256(const uint8_t *data, uint64_t sz, uint8_t *out) {
+  fdt_sha256_t s;
+  fdt_sha256_init(&s);
+  fdt_sha256_append(&s, data, sz);
+  fdt_sha256_fini(&s, out);
+}
+
+int fdgpu_shreds_verify(fdgpu_verifier_t v, const uint8_t *arena, uint64_t arena_sz, const fdgpu_shred_t *shreds,
+                        uint64_t n, uint16_t expected_version, uint64_t batch_max, int8_t *codes, uint8_t *roots) {
+  if (!v.submit || !v.poll || !codes || (n && (!arena || !shreds)) || !batch_max) return FDGPU_ERR_INVAL;
+  for (uint64_t i = 0; i < n; i++)
+    if ((uint64_t)shreds[i].off + shreds[i].sz > arena_sz || (uint64_t)shreds[i].pub_off + 32 > arena_sz)
+      return FDGPU_ERR_INVAL;
+  /* the roots first, shreds dealt to the threads in runs of 256 (a shred's hash is ~40 SHA-256 blocks) */
+  std::vector<uint8_t> own;
+  if (!roots) { own.resize(32 * std::max<uint64_t>(n, 1)); roots = own.data(); }
+  std::vector<uint8_t> ok(std::max<uint64_t>(n, 1));
+  std::atomic<uint64_t> next{0};
+  auto work = [&] {
+    for (uint64_t b; (b = next.fetch_add(256)) < n;)
+      for (uint64_t i = b; i < std::min(n, b + 256); i++) {
+        fdt_shred_chk_t chk;
+        ok[i] = (uint8_t)fdt_shred_check_core(arena + shreds[i].off, shreds[i].sz, expected_version, &chk);
+        if (ok[i]) fdt_shred_root_core(arena + shreds[i].off, &chk, roots + 32 * i);
+        else memset(roots + 32 * i, 0, 32);
+      }
+  };
+  const unsigned hw = std::thread::hardware_concurrency();
+  const uint64_t nt = std::min<uint64_t>({16, hw ? hw : 1, (n + 1023) / 1024});
+  std::vector<std::thread> th;
+  for (uint64_t t = 1; t < nt; t++) th.emplace_back(work);
+  work();
+  for (auto &t : th) t.join();
+  Pipe p(v, codes);
+  Chunk *c = nullptr;
+  int r = p.next(&c);
+  for (uint64_t i = 0; i < n && !r; i++) {
+    if (!ok[i]) { codes[i] = FDGPU_CODE_SHRED_REJECT; continue; }
+    if (c->txns.size() == batch_max) {
+      r = p.submit(*c);
+      if (!r) r = p.next(&c);
+      if (r) break;
+    }
+    /* item = sig[64] | pub[32] | root[32], as fdgpu_fec_roots_verify */
+    const uint32_t base = (uint32_t)c->arena.size();
+    const uint8_t *sh = arena + shreds[i].off, *pk = arena + shreds[i].pub_off;
+    c->arena.insert(c->arena.end(), sh, sh + 64);
     c->arena.insert(c->arena.end(), pk, pk + 32);
     c->arena.insert(c->arena.end(), roots + 32 * i, roots + 32 * i + 32);
     fdgpu_txn_t d;

@@ -36,6 +36,9 @@ TXN_DTYPE = np.dtype([("msg_off", "<u4"), ("msg_sz", "<u4"), ("sig_off", "<u4"),
 SIG_DESC_DTYPE = np.dtype([("msg_off", "<u4"), ("msg_sz", "<u4"), ("sig_off", "<u4"), ("pub_off", "<u4")])
 TXN_DESC_DTYPE = np.dtype([("sig0", "<u4"), ("sig_cnt", "<u4")])
 ARENA_SLACK = 160
+SHRED_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("pub_off", "<u4")])   # fdgpu_shred_t
+CODE_SHRED_REJECT = -67       # FDGPU_CODE_SHRED_REJECT
+SHRED_SZ_MAX = 1228 + 4       # FDGPU_SHRED_SZ_MAX
 
 
 def verify(msg, sig, public_key, sha=None):
@@ -251,6 +254,34 @@ class VerifyEngine:
         del self._pending[ticket]
         return codes[:n], tags[:n], osz[:n]
 
+    def submit_shreds(self, arena, shreds, expected_version):
+        """fdgpu_submit_shreds: raw Merkle shreds (SHRED_DTYPE {off, sz,
+        pub_off}) checked, hashed to their roots and verified on the GPU."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        shreds = np.ascontiguousarray(shreds, dtype=SHRED_DTYPE)
+        tk = _lib.lib().fdgpu_submit_shreds(self._h, arena.ctypes.data, arena.size, shreds.ctypes.data, len(shreds),
+                                            int(expected_version))
+        if tk < 0:
+            raise RuntimeError(f"fdgpu_submit_shreds failed ({tk}): {_lib.last_error()}")
+        self._pending[tk] = len(shreds)
+        return tk
+
+    def poll_shreds(self, ticket, blocking=True):
+        """-> (codes int8[n], roots uint8[n, 32]) or None while pending."""
+        n = self._pending[ticket]
+        codes = np.zeros(max(n, 1), dtype=np.int8)
+        roots = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        rc = _lib.lib().fdgpu_poll_shreds(self._h, ticket, codes.ctypes.data, roots.ctypes.data, 1 if blocking else 0)
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise RuntimeError(f"fdgpu_poll_shreds failed ({rc}): {_lib.last_error()}")
+        del self._pending[ticket]
+        return codes[:n], roots[:n]
+
+    def verify_shreds(self, arena, shreds, expected_version):
+        return self.poll_shreds(self.submit_shreds(arena, shreds, expected_version), blocking=True)
+
     def verify_device(self, d_arena, d_sig_desc, n_sig, d_txn_desc, n_txn, d_sig_codes, d_txn_codes, stream=0):
         """Device-resident path; all pointers are device addresses (ints)."""
         rc = _lib.lib().fdgpu_verify_device(self._h, d_arena, d_sig_desc, n_sig, d_txn_desc, n_txn,
@@ -297,6 +328,38 @@ class VerifyEngine:
         self._chk(_lib.lib().fdgpu_debug_sha512(self._h, arena.ctypes.data, arena.size, txns.ctypes.data, len(txns),
                                                 out.ctypes.data), "debug_sha512")
         return out
+
+    def debug_sha256(self, arena, txns):
+        """SHA-256 of arena[msg_off, +msg_sz) per record -> uint8[n, 32] (the shred path's hash)"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=TXN_DTYPE)
+        out = np.zeros((len(txns), 32), dtype=np.uint8)
+        self._chk(_lib.lib().fdgpu_debug_sha256(self._h, arena.ctypes.data, arena.size, txns.ctypes.data, len(txns),
+                                                out.ctypes.data), "debug_sha256")
+        return out
+
+    def debug_shred_roots(self, arena, shreds, expected_version):
+        """The shred checks and Merkle roots alone -> (ok int8[n]: 0 or
+        CODE_SHRED_REJECT, roots uint8[n, 32])"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        shreds = np.ascontiguousarray(shreds, dtype=SHRED_DTYPE)
+        ok = np.zeros(len(shreds), dtype=np.int8)
+        roots = np.zeros((len(shreds), 32), dtype=np.uint8)
+        self._chk(_lib.lib().fdgpu_debug_shred_roots(self._h, arena.ctypes.data, arena.size, shreds.ctypes.data,
+                                                     len(shreds), int(expected_version), ok.ctypes.data,
+                                                     roots.ctypes.data), "debug_shred_roots")
+        return ok, roots
+
+    def debug_shred_time(self, arena, shreds, expected_version, iters=5):
+        """-> (ingest_ms, verify_ms): mean device time of the batch's ingest
+        and of its verify, the batch resident in HBM"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        shreds = np.ascontiguousarray(shreds, dtype=SHRED_DTYPE)
+        a, v = ctypes.c_double(), ctypes.c_double()
+        self._chk(_lib.lib().fdgpu_debug_shred_time(self._h, arena.ctypes.data, arena.size, shreds.ctypes.data,
+                                                    len(shreds), int(expected_version), int(iters), ctypes.byref(a),
+                                                    ctypes.byref(v)), "debug_shred_time")
+        return a.value, v.value
 
     def debug_hram(self, arena, txns):
         arena = np.ascontiguousarray(arena, dtype=np.uint8)

@@ -93,6 +93,16 @@ FRAG_EX_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("tr_off", "<u4"), ("tr
 CODE_PARSE_FAIL, CODE_TRAILER_CAP = -64, -65
 
 
+SHRED_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("pub_off", "<u4")])   # fdgpu_shred_t
+CODE_SHRED_REJECT = -67
+
+
+class ShredChk(c.Structure):
+    """fdt_shred_chk_t"""
+    _fields_ = [("shred_idx", c.c_uint32), ("depth", c.c_uint32), ("proof_off", c.c_uint32),
+                ("leaf_off", c.c_uint32), ("leaf_end", c.c_uint32)]
+
+
 class Verifier(c.Structure):
     """fdgpu_verifier_t: submit/poll, plus the optional zero-copy staging
     hooks (left NULL by PyVerifier; set by the GPU dispatcher)."""
@@ -280,6 +290,10 @@ def lib():
         "fdgpu_producer_start": (vp, [vp, u64, u64, vp, u64, u64, vp, vp, vp, u64, c.c_double]),
         "fdgpu_replay_verify": (c.c_int, [Verifier, vp, vp, vp, u64, u64, u64, vp]),
         "fdgpu_fec_roots_verify": (c.c_int, [Verifier, vp, vp, vp, c.c_int, u64, u64, vp]),
+        "fdgpu_shreds_verify": (c.c_int, [Verifier, vp, u64, vp, u64, c.c_uint16, u64, vp, vp]),
+        "fdt_shred_check": (c.c_int, [vp, u64, c.c_uint16, c.POINTER(ShredChk)]),
+        "fdt_shred_root": (None, [vp, c.POINTER(ShredChk), vp]),
+        "fdt_sha256": (None, [vp, u64, vp]),
         "fdt_tpu_reasm_footprint": (u64, [u64, u64]),
         "fdt_tpu_reasm_new": (vp, [vp, u64, u64, u64]),
         "fdt_tpu_reasm_reset": (None, [vp]),
@@ -1032,6 +1046,53 @@ def fec_roots_verify(verifier, roots, sigs, pubkeys, batch_max=65536):
     if r:
         raise RuntimeError(f"fdgpu_fec_roots_verify failed: {r}")
     return codes[:n]
+
+
+def sha256(data):
+    """The host library's SHA-256 (fdt_sha256) -> 32 bytes"""
+    data = bytes(data)
+    out = c.create_string_buffer(32)
+    lib().fdt_sha256(data, len(data), out)
+    return out.raw
+
+
+def shred_check(buf, expected_version):
+    """fdt_shred_check: the shred tile's checks before the signature ->
+    {shred_idx, depth, proof_off, leaf_off, leaf_end}, or None if dropped.
+    The buffer handed over holds exactly len(buf) bytes."""
+    buf = bytes(buf)
+    raw = (c.c_uint8 * max(len(buf), 1)).from_buffer_copy(buf or b"\0")
+    chk = ShredChk()
+    if not lib().fdt_shred_check(raw, len(buf), int(expected_version), c.byref(chk)):
+        return None
+    return {k: getattr(chk, k) for k, _ in ShredChk._fields_}
+
+
+def shred_root(buf, expected_version):
+    """fdt_shred_check + fdt_shred_root -> the 32-byte Merkle root, or None if dropped"""
+    buf = bytes(buf)
+    raw = (c.c_uint8 * max(len(buf), 1)).from_buffer_copy(buf or b"\0")
+    chk = ShredChk()
+    if not lib().fdt_shred_check(raw, len(buf), int(expected_version), c.byref(chk)):
+        return None
+    out = c.create_string_buffer(32)
+    lib().fdt_shred_root(raw, c.byref(chk), out)
+    return out.raw
+
+
+def shreds_verify(verifier, arena, shreds, expected_version, batch_max=65536):
+    """Raw shreds to verdicts over any verifier, roots hashed on the host
+    (fdgpu_shreds_verify) -> (codes int8[n], roots uint8[n, 32])"""
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    shreds = np.ascontiguousarray(shreds, dtype=SHRED_DTYPE)
+    n = len(shreds)
+    codes = np.zeros(max(n, 1), dtype=np.int8)
+    roots = np.zeros((max(n, 1), 32), dtype=np.uint8)
+    r = lib().fdgpu_shreds_verify(verifier.struct, arena.ctypes.data, arena.size, shreds.ctypes.data, n,
+                                  int(expected_version), batch_max, codes.ctypes.data, roots.ctypes.data)
+    if r:
+        raise RuntimeError(f"fdgpu_shreds_verify failed: {r}")
+    return codes[:n], roots[:n]
 
 
 # ------------------------------------------------------------------ tiles

@@ -41,6 +41,7 @@
 #include <stdint.h>
 
 #include "fd_ed25519_gpu.h"
+#include "fd_shred_gpu.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -703,6 +704,37 @@ int fdgpu_replay_verify( fdgpu_verifier_t v, uint8_t const * payloads, uint64_t 
 int fdgpu_fec_roots_verify( fdgpu_verifier_t v, uint8_t const * roots, uint8_t const * sigs,
                             uint8_t const * pubkeys, int shared_pubkey, uint64_t n, uint64_t batch_max,
                             int8_t * codes );
+
+/* Raw shreds (fd_fec_resolver_add_shred's path for the first shred of an FEC
+   set, src/disco/shred/fd_fec_resolver.c:333-443), the rules of
+   firedancer_amd/csrc/fdt_shred.h compiled for the host.
+
+   fdt_shred_check: 1 and *out filled if buf[0, sz) passes fd_shred_parse and
+   every resolver check before the signature, else 0.  The leaf is
+   buf[leaf_off, leaf_end), the proof's depth 20-byte nodes start at
+   proof_off.  fdt_shred_root: the 32-byte Merkle root of a shred that
+   passed.  fdt_sha256: SHA-256 of data[0, sz). */
+typedef struct {
+  uint32_t shred_idx;     /* the shred's leaf in its FEC set's tree */
+  uint32_t depth;         /* proof nodes (the variant's low four bits) */
+  uint32_t proof_off;
+  uint32_t leaf_off;      /* 64: past the signature */
+  uint32_t leaf_end;      /* == proof_off */
+} fdt_shred_chk_t;
+int  fdt_shred_check( uint8_t const * buf, uint64_t sz, uint16_t expected_version, fdt_shred_chk_t * out );
+void fdt_shred_root( uint8_t const * buf, fdt_shred_chk_t const * chk, uint8_t * root );
+void fdt_sha256( uint8_t const * data, uint64_t sz, uint8_t * out );
+
+/* Shreds to verdicts over any verifier, the roots computed on the host (up
+   to 16 threads): shred i = arena[off, off+sz) with its leader's key at
+   pub_off (fd_shred_gpu.h).  codes[i] = what fd_ed25519_verify(root, 32,
+   shred, leader) returns, or FDGPU_CODE_SHRED_REJECT for a shred the checks
+   drop; roots (NULL: not wanted) 32 n bytes, zeros for a rejected shred.
+   Verified in batches of <= batch_max, two in flight.  The engine's
+   fdgpu_submit_shreds does the same with the hashes on the device; this is
+   the host-hash baseline it is measured against.  Returns 0 or < 0. */
+int fdgpu_shreds_verify( fdgpu_verifier_t v, uint8_t const * arena, uint64_t arena_sz, fdgpu_shred_t const * shreds,
+                         uint64_t n, uint16_t expected_version, uint64_t batch_max, int8_t * codes, uint8_t * roots );
 
 /* --------------------------------------- process separation (§8(f) row 1) */
 
