@@ -317,6 +317,8 @@ fdgpu_engine_t *fdgpu_engine_open(int device, fdgpu_cfg_t const *cfg_in) {
   int bpcu = 0;
   hipDeviceProp_t prop;
   if (fdgpu_verify_occupancy(&bpcu) != hipSuccess || bpcu < 1) bpcu = 1;
+  /* the comb build and the occupancy query loaded their units' kernels; the ingest unit's too, before the first batch */
+  if (fdgpu_ingest_load() != hipSuccess) { set_err("ingest kernels"); return fail(); }
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) { set_err("props"); return fail(); }
   e->resident_blocks = (uint32_t)(bpcu * prop.multiProcessorCount);
   {

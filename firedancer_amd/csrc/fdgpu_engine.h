@@ -51,7 +51,7 @@ inline bool env_eq(const char *v, const char *s) { return v && !strcmp(v, s); }
 inline long long env_num(const char *v, long long dflt, int base = 10) { return v ? strtoll(v, nullptr, base) : dflt; }
 
 /* Every switch the engine reads from the environment, with its default (the synchronous API's four are SyncEnv in
-   fdgpu_sync.cpp; the kernels' own FDGPU_AUX_BLOCKS_IN / _FIN stay in fdgpu_kernels.hip).  Constructing an Env reads
+   fdgpu_sync.cpp; the kernels' own FDGPU_AUX_BLOCKS_IN / _FIN stay in fdgpu_ingest.hip).  Constructing an Env reads
    them all; the moment a switch counts is the moment of the Env it is taken from:
      load  g_env, constructed when the library is loaded
      open  a fresh Env in each fdgpu_engine_open (and, for the two debug ones, in each fdgpu_build_info) */

@@ -1,5 +1,6 @@
-/* fdgpu_internal.h -- declarations shared by the kernels (fdgpu_kernels.hip)
-   and the host engine (fdgpu_engine.h).  Not part of the public C ABI. */
+/* fdgpu_internal.h -- declarations shared by the kernel units (fdgpu_bcomb,
+   fdgpu_verify, fdgpu_ingest, fdgpu_test_kernels .hip) and the host engine
+   (fdgpu_engine.h).  Not part of the public C ABI. */
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -32,6 +33,20 @@ typedef struct {
 #ifndef FDGPU_ATAB_WORDS
 #define FDGPU_ATAB_WORDS    40u           /* u32 per cached entry (a diagnostic build may pad it) */
 #endif
+#ifndef FDGPU_VERIFY_WAVES
+#define FDGPU_VERIFY_WAVES  2             /* waves per SIMD of the verify kernel: decode/pow chains want ~190 VGPRs */
+#endif
+#ifndef FDGPU_PHASE_STAMPS
+#define FDGPU_PHASE_STAMPS  0             /* 1: per-phase cycle stamps (fdgpu_stamps.h), a diagnostic build */
+#endif
+/* Build switches: FDGPU_VERIFY_WAVES, FDGPU_ATAB_WORDS and FDGPU_PHASE_STAMPS,
+   their defaults stated here once for every unit.  The shipped library is
+   built with every one at its default;
+   fdgpu_build_info() reports them and smoke() / bench.py refuse a library
+   built otherwise (unless told it is an A/B build).  The slot-indexed
+   workspace pool and the table store / load cache-policy switches were
+   removed after their negative results (commit a5516cc is the
+   last that holds them). */
 /* Fixed-base comb for [S]B: S in signed radix 2^W, digit i looked up in
    table i = {0, 1, .., 2^(W-1)} x 2^(W i) B (affine niels, one 128-B line per
    entry), so [S]B costs NDIG mixed additions and no doublings.  Tables live
@@ -92,10 +107,15 @@ typedef struct {
 extern "C" {
 #endif
 
-/* launchers (fdgpu_kernels.hip); all asynchronous on `stream` unless noted */
+/* Launchers, under the unit that defines each with its kernels; all
+   asynchronous on `stream` unless noted */
+
+/* ---- fdgpu_bcomb.hip ---- */
 size_t     fdgpu_btab_bytes(void);                                   /* fixed-base table size */
 /* builds the fixed-base table into d_btab (fdgpu_btab_bytes()); synchronous */
 hipError_t fdgpu_btab_build(uint32_t *d_btab, hipStream_t stream);
+
+/* ---- fdgpu_verify.hip ---- */
 /* one signature per lane; d_ws must hold fdgpu_ws_bytes(n_sig) bytes */
 /* d_perm (NULL = identity): d_sig_codes[d_perm[i]] receives the code of
    descriptor i (descriptors grouped by SHA-512 block count, codes in the
@@ -178,14 +198,9 @@ hipError_t fdgpu_verify_occupancy(int *blocks_per_cu);
 int        fdgpu_kernel_build_info(char *buf, size_t n);
 size_t     fdgpu_ws_bytes(uint64_t n_sig);
 
-/* test/diagnostic kernels */
-hipError_t fdgpu_launch_test_fe(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
-hipError_t fdgpu_launch_test_decode(const uint32_t *d_enc, uint32_t *d_out, uint32_t n, uint32_t flags, hipStream_t stream);
-hipError_t fdgpu_launch_test_sha512(const uint8_t *d_arena, const fdgpu_sig_desc_t *d_msgs, uint32_t n,
-                                    uint32_t *d_out, hipStream_t stream);
-hipError_t fdgpu_launch_test_hram(const uint8_t *d_arena, const fdgpu_sig_desc_t *d_sigs, uint32_t n,
-                                  uint32_t *d_out, hipStream_t stream);
-hipError_t fdgpu_launch_test_sc_reduce(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
+/* ---- fdgpu_ingest.hip ---- */
+/* loads the unit's code object (engine open: before the first frag batch) */
+__attribute__((visibility("hidden"))) hipError_t fdgpu_ingest_load(void);
 /* GPU-side ingest: parse n raw payloads (frags index d_arena), scan the
    signature counts, expand the descriptors; the batch's signature count is
    left in *d_n_sig.  Buffers: d_txn_out n x FDT_TXN_MAX_SZ, d_txn_sz /
@@ -244,6 +259,15 @@ hipError_t fdgpu_launch_frag_finish_io(const fdgpu_txn_desc_t *d_tds, uint32_t n
                                        const uint8_t *d_arena, uint64_t hash_seed, uint8_t *d_out, int8_t *d_codes,
                                        uint64_t *d_tags, uint16_t *d_out_szs, uint32_t *d_zero_next,
                                        hipStream_t stream);
+
+/* ---- fdgpu_test_kernels.hip: per-stage diagnostics ---- */
+hipError_t fdgpu_launch_test_fe(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
+hipError_t fdgpu_launch_test_decode(const uint32_t *d_enc, uint32_t *d_out, uint32_t n, uint32_t flags, hipStream_t stream);
+hipError_t fdgpu_launch_test_sha512(const uint8_t *d_arena, const fdgpu_sig_desc_t *d_msgs, uint32_t n,
+                                    uint32_t *d_out, hipStream_t stream);
+hipError_t fdgpu_launch_test_hram(const uint8_t *d_arena, const fdgpu_sig_desc_t *d_sigs, uint32_t n,
+                                  uint32_t *d_out, hipStream_t stream);
+hipError_t fdgpu_launch_test_sc_reduce(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
 hipError_t fdgpu_launch_test_hs_split(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
 
 #ifdef __cplusplus

@@ -27,7 +27,7 @@
    more; up to 159 bits (40 windows) run in the verify kernel, and only a
    lane whose Euclid needs a full-precision step with a quotient >= 2^31
    (probability ~2^-30 per step) takes the full-length path
-   (fdgpu_kernels.hip, fdgpu_full_kernel).  The Euclid itself runs as
+   (fdgpu_verify.hip, fdgpu_full_kernel).  The Euclid itself runs as
    Lehmer's algorithm (hs_split below).
 
    Per lane, 32-bit limbs; __host__ __device__ so tests/test_lattice.py can

@@ -1,7 +1,7 @@
 /* fdgpu_shred.hip -- raw Merkle shreds on the device (include/fd_shred_gpu.h):
    the shred tile's checks, the SHA-256 Merkle leaf, the walk up the inclusion
-   proof, and the records the verify kernels (fdgpu_kernels.hip, untouched)
-   take from there.
+   proof, and the records the verify kernels (fdgpu_verify.hip) take from
+   there.
 
      ingest  one shred per lane: fdt_shred_check (fdt_shred.h, the host
              library's own source), the leaf hash over the ~1.1 KB between the

@@ -1,10 +1,10 @@
 """Opcode-class histogram of one kernel's loops, from the gfx950 assembly
-(make -C firedancer_amd/csrc asm).  Finds the loops by their back edges
+(make -C firedancer_amd/csrc asm: one .s per kernel unit).  Finds the loops by their back edges
 (a branch to an earlier label), prints each loop's size and instruction
 classes, and -- with --weights 'LINE:TRIPS,...' -- a trip-weighted total per
 class for the loops named by their first line.
 
-    python tools/isa_hist.py firedancer_amd/csrc/fdgpu_kernels.s \
+    python tools/isa_hist.py firedancer_amd/csrc/obj/fdgpu_verify.s \
         --kernel _ZN12_GLOBAL__N_122fdgpu_verify_hs_kernelILb0E [--weights 12345:33]
 """
 import argparse

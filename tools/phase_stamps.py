@@ -4,7 +4,7 @@
     FDGPU_LIB=build/stamps/libfd_ed25519_gpu.so python tools/phase_stamps.py [--txns N] [--out f.json]
 
 Lane 0 of every wave stamps the shader clock at the phase boundaries of
-fdgpu_kernels.hip (FDGPU_STAMP 0..7, fdgpu_stamps.h).  Reported: the mean
+fdgpu_verify.hip (FDGPU_STAMP 0..7, fdgpu_stamps.h).  Reported: the mean
 cycles each wave spends per phase (two waves share a SIMD, so a phase's
 cycles include the time the partner wave held the VALU), the share of the
 wave's lifetime, and the kernel's HIP-event time.
