@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FDGPU_LIB") or os.path.join(_HERE, "libfd_ed25519_gpu.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_ed25519_gpu.h")
 SHRED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_shred_gpu.h")
+POH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_poh_gpu.h")
 
 _LIB = None
 
@@ -149,6 +150,20 @@ def lib():
     L.fdgpu_debug_shred_time.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint16, c.c_int,
                                          c.POINTER(c.c_double), c.POINTER(c.c_double)]
     L.fdgpu_debug_shred_time.restype = c.c_int
+    # include/fd_poh_gpu.h
+    L.fdgpu_submit_poh.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, vp, c.c_uint64, c.c_uint64]
+    L.fdgpu_submit_poh.restype = c.c_int64
+    L.fdgpu_poll_poh.argtypes = [vp, c.c_int64, vp, vp, c.c_int]
+    L.fdgpu_poll_poh.restype = c.c_int
+    L.fdgpu_poh_limits.argtypes = [vp] + [c.POINTER(c.c_uint64)] * 3
+    L.fdgpu_poh_limits.restype = c.c_int
+    L.fdgpu_poh_chunk.argtypes = []
+    L.fdgpu_poh_chunk.restype = c.c_uint32
+    L.fdgpu_debug_poh.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, vp, c.c_uint64, c.c_uint64, c.c_uint32, vp, vp]
+    L.fdgpu_debug_poh.restype = c.c_int
+    L.fdgpu_debug_poh_time.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, vp, c.c_uint64, c.c_uint64, c.c_int,
+                                       c.POINTER(c.c_double), c.POINTER(c.c_double)]
+    L.fdgpu_debug_poh_time.restype = c.c_int
     for fn in ("fdgpu_debug_fe_ops", "fdgpu_debug_decode", "fdgpu_debug_sha512", "fdgpu_debug_hram",
                "fdgpu_debug_sc_reduce", "fdgpu_debug_hs_split", "fdgpu_debug_sig_codes"):
         getattr(L, fn).restype = c.c_int

@@ -1,8 +1,8 @@
 /* fdgpu_engine.h -- what the host engine's units share (fdgpu_engine.cpp, fdgpu_ring.cpp, fdgpu_frags.cpp,
-   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp, fdgpu_shreds.cpp): the error text, the environment switches,
+   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp, fdgpu_shreds.cpp, fdgpu_poh_batch.cpp): the error text, the environment switches,
    the owners of HIP memory, the ring's slot and the engine, the host-side buffer layouts, and the few internals more
    than one unit calls.  Everything here has hidden visibility: the exported C ABI is include/fd_ed25519_gpu.h and its
-   extension include/fd_shred_gpu.h, nothing else (tests/test_abi.py).  The kernels do not include this file. */
+   extensions include/fd_shred_gpu.h and include/fd_poh_gpu.h, nothing else (tests/test_abi.py).  The kernels do not include this file. */
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/fd_ed25519_gpu.h"
+#include "../../include/fd_poh_gpu.h"
 #include "../../include/fd_shred_gpu.h"
 #include "fdgpu_internal.h"
 #include "fdt_parse.h"
@@ -141,6 +142,7 @@ enum class Batch : uint8_t {
   Frag,     /* fdgpu_submit_frags: [codes][trailers] in h_tr */
   FragIo,   /* fdgpu_submit_frags_io: io_results() in h_tr */
   Shred,    /* fdgpu_submit_shreds: [codes, padded to 64][roots] in h_shres */
+  Poh,      /* fdgpu_submit_poh: [codes, padded to 64][hashes] in h_pres */
 };
 
 struct Slot {
@@ -194,6 +196,13 @@ struct Slot {
   HostBuf<fdgpu_shred_t> h_sh; DevBuf<fdgpu_shred_t> d_sh;
   DevBuf<uint32_t> d_sh_cnt;
   DevBuf<uint8_t> d_shres; HostBuf<uint8_t> h_shres;
+  /* PoH batches (fdgpu_submit_poh), allocated on the slot's first one for max_txn entries and max_sig signatures:
+     the entries, the signatures' arena offsets, the queue (entry indices, longest chain first) and its head, the
+     tree's nodes (32 B per signature), and the results [codes, padded to 64][32-B hashes] with their pinned
+     read-back */
+  HostBuf<fdgpu_poh_entry_t> h_pe; DevBuf<fdgpu_poh_entry_t> d_pe;
+  HostBuf<uint32_t> h_psig, h_pord; DevBuf<uint32_t> d_psig, d_pord, d_pnodes, d_phead;
+  DevBuf<uint8_t> d_pres; HostBuf<uint8_t> h_pres;
   /* FDGPU_FLAG_MERGE: the batch's gather + parse are queued and its verify waits to be merged with the other batches
      ready (merge_kick), which then queues the rest of the batch behind it */
   hipEvent_t parsed = nullptr;

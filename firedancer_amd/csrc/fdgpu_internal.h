@@ -1,5 +1,5 @@
 /* fdgpu_internal.h -- declarations shared by the kernel units (fdgpu_bcomb,
-   fdgpu_verify, fdgpu_ingest, fdgpu_test_kernels .hip) and the host engine
+   fdgpu_verify, fdgpu_ingest, fdgpu_test_kernels, fdgpu_poh .hip) and the host engine
    (fdgpu_engine.h).  Not part of the public C ABI. */
 #pragma once
 
@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/fd_ed25519_gpu.h"
+#include "../../include/fd_poh_gpu.h"
 
 /* Per-signature work item (16 B, one dwordx4 per lane).  Offsets index the
    batch arena; the arena carries FDGPU_ARENA_SLACK readable bytes after
@@ -102,6 +103,11 @@ typedef struct {
 /* SHA-512 block-count groups of the host-side bucketing (expand): messages of
    more blocks than this share the last group */
 #define FDGPU_NBLK_GROUPS   32u
+/* PoH chains (fdgpu_poh.hip): hashes a lane runs between two looks at the entry
+   queue.  64 hashes are ~10^5 instructions, against which the ballot and the
+   finished lanes' mixin and stores are noise; a finished lane idles for at
+   most this many hashes of its wave */
+#define FDGPU_POH_CHUNK     64u
 
 #ifdef __cplusplus
 extern "C" {
@@ -259,6 +265,24 @@ hipError_t fdgpu_launch_frag_finish_io(const fdgpu_txn_desc_t *d_tds, uint32_t n
                                        const uint8_t *d_arena, uint64_t hash_seed, uint8_t *d_out, int8_t *d_codes,
                                        uint64_t *d_tags, uint16_t *d_out_szs, uint32_t *d_zero_next,
                                        hipStream_t stream);
+
+/* ---- fdgpu_poh.hip (the shred unit's launchers: fdgpu_shred.h) ---- */
+/* Leaves and roots of a PoH batch: d_nodes (8 u32 a node, 16-B aligned, one
+   per signature) receives SHA-256(0x00 || arena[d_sig_offs[j], +64)) as
+   big-endian words, then each entry's range is folded in place and its root
+   left in node sig_first.  Reads up to 16 bytes past a signature (the arena's
+   slack). */
+hipError_t fdgpu_launch_poh_tree(const uint8_t *d_arena, const fdgpu_poh_entry_t *d_entries, uint32_t n,
+                                 const uint32_t *d_sig_offs, uint32_t sig_total, uint32_t *d_nodes, hipStream_t stream);
+/* The chains, after the tree on the same stream: d_order[0, n_q) are the
+   entries with hash_cnt <= cap, longest first; *d_head (cleared here, on the
+   stream) is the queue's head.  grid_waves: the grid in waves (0: one per 64
+   entries, at most four per SIMD).  d_codes[i] and d_hashes + 32 i (16-B
+   aligned) for every entry, those above the cap included. */
+hipError_t fdgpu_launch_poh_chains(const uint8_t *d_arena, const fdgpu_poh_entry_t *d_entries, uint32_t n,
+                                   const uint32_t *d_order, uint32_t n_q, const uint32_t *d_nodes, uint32_t cap,
+                                   uint32_t grid_waves, uint32_t *d_head, int8_t *d_codes, uint8_t *d_hashes,
+                                   hipStream_t stream);
 
 /* ---- fdgpu_test_kernels.hip: per-stage diagnostics ---- */
 hipError_t fdgpu_launch_test_fe(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);

@@ -250,6 +250,10 @@ int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking
       if (txn_codes && n) memcpy(txn_codes, s->h_shres, n);
       if (roots && n) memcpy(roots, s->h_shres + s->tr_base, n * 32);
       break;
+    case Batch::Poh:
+      if (txn_codes && n) memcpy(txn_codes, s->h_pres, n);
+      if (roots && n) memcpy(roots, s->h_pres + s->tr_base, n * 32);
+      break;
   }
   if (keep) st_rlx(s->held, true);
   else st_rlx(s->ticket, (int64_t)-1);

@@ -1,7 +1,9 @@
 /* fdgpu_sha256.h -- one-message-per-lane SHA-256 (FIPS 180-4) on gfx950, for
    the shred path (fdgpu_shred.hip): the Merkle leaf hash of a shred (about
    1.1 KB behind a 26-byte constant prefix) and the node hashes of its
-   inclusion proof (a fixed 66-byte, two-block message).
+   inclusion proof (a fixed 66-byte, two-block message); and for the PoH path
+   (fdgpu_poh.hip): the chain's hash of 32 bytes, the 65-byte leaf and branch
+   of the 32-byte signature tree, the 64-byte mixin.
 
    The state and the 16-word message schedule live in VGPRs; rotates are
    v_alignbit_b32, the three-input xors, Ch and Maj one v_bitop3_b32 each.
@@ -170,6 +172,84 @@ FDG_DEV void sha256_node(uint32_t (&h)[8], const uint32_t (&l)[5], const uint32_
 #pragma unroll
   for (int t = 1; t < 15; t++) w[t] = 0u;
   w[15] = 66u * 8u;
+  sha256_compress(h, w);
+}
+
+/* ---- the PoH path (fdgpu_poh.hip) ---- */
+
+/* One block from the initial state with every round unrolled: the round
+   constants become literals, and whatever part of the state and of the
+   schedule depends only on constant message words is folded at compile time.
+   h receives the digest words. */
+FDG_DEV void sha256_compress_unrolled(uint32_t (&h)[8], uint32_t (&w)[16]) {
+  constexpr uint32_t IV[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                              0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+  uint32_t a = IV[0], b = IV[1], c = IV[2], d = IV[3], e = IV[4], f = IV[5], g = IV[6], hh = IV[7];
+#pragma unroll
+  for (int r = 0; r < 64; r++) {
+    const int t = r & 15;
+    if (r >= 16) {
+      const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
+      const uint32_t s0 = xor3_32(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3);
+      const uint32_t s1 = xor3_32(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
+      w[t] += s0 + w[(t + 9) & 15] + s1;
+    }
+    const uint32_t t1 = hh + xor3_32(rotr32(e, 6), rotr32(e, 11), rotr32(e, 25)) + ch32(e, f, g) + SHA256_K[r] + w[t];
+    const uint32_t t2 = xor3_32(rotr32(a, 2), rotr32(a, 13), rotr32(a, 22)) + maj32(a, b, c);
+    hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+  }
+  h[0] = IV[0] + a; h[1] = IV[1] + b; h[2] = IV[2] + c; h[3] = IV[3] + d;
+  h[4] = IV[4] + e; h[5] = IV[5] + f; h[6] = IV[6] + g; h[7] = IV[7] + hh;
+}
+
+/* One step of the PoH chain: h = SHA-256(h as 32 bytes).  The 8 state words
+   of one hash are the 8 message words of the next, so a chain stays in
+   registers and never swaps bytes; words 8..15 of its single block are the
+   padding (0x80000000, zeros, the length 256), constants the schedule is
+   folded over. */
+FDG_DEV void sha256_hash32(uint32_t (&h)[8]) {
+  uint32_t w[16];
+#pragma unroll
+  for (int t = 0; t < 8; t++) w[t] = h[t];
+  w[8] = 0x80000000u;
+#pragma unroll
+  for (int t = 9; t < 15; t++) w[t] = 0u;
+  w[15] = 256u;
+  sha256_compress_unrolled(h, w);
+}
+
+/* SHA-256(prefix (1 B) || m[0,64)), 65 bytes, always two blocks: the Merkle
+   leaf (prefix 0, m a signature loaded with sha256_load_words) and branch
+   (prefix 1, m two 32-byte nodes) of the 32-byte tree.  m is 16 big-endian
+   words.  The first block is m shifted by one byte behind the prefix; the
+   second is m's last byte, the 0x80 and the length -- constant but for that
+   byte. */
+FDG_DEV void sha256_hash65(uint32_t (&h)[8], uint32_t prefix, const uint32_t (&m)[16]) {
+  uint32_t w[16];
+  w[0] = (prefix << 24) | (m[0] >> 8);
+#pragma unroll
+  for (int t = 1; t < 16; t++) w[t] = __builtin_amdgcn_alignbit(m[t - 1], m[t], 8);
+  sha256_init(h);
+  sha256_compress(h, w);
+  w[0] = (m[15] << 24) | 0x00800000u;
+#pragma unroll
+  for (int t = 1; t < 15; t++) w[t] = 0u;
+  w[15] = 65u * 8u;
+  sha256_compress(h, w);
+}
+
+/* The PoH mixin: h = SHA-256(h[32] || m[32]), 64 bytes, two blocks, the
+   second one the padding alone */
+FDG_DEV void sha256_mix64(uint32_t (&h)[8], const uint32_t (&m)[8]) {
+  uint32_t w[16];
+#pragma unroll
+  for (int t = 0; t < 8; t++) { w[t] = h[t]; w[8 + t] = m[t]; }
+  sha256_init(h);
+  sha256_compress(h, w);
+  w[0] = 0x80000000u;
+#pragma unroll
+  for (int t = 1; t < 15; t++) w[t] = 0u;
+  w[15] = 64u * 8u;
   sha256_compress(h, w);
 }
 

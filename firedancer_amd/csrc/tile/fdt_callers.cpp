@@ -12,7 +12,13 @@
               (32-byte messages, single signatures);
               fdgpu_shreds_verify starts from the raw shreds: the checks
               before the signature and the SHA-256 Merkle root on the host
-              (fdt_shred.h), then the same batched verify.
+              (fdt_shred.h), then the same batched verify;
+     poh      fd_runtime_block_verify_tpool (src/flamenco/runtime/
+              fd_runtime.c:2274-2371) hashes every microblock's chain, builds
+              the Merkle root of its signatures and mixes it in;
+              fdgpu_block_poh_verify takes the entries of many blocks and
+              their raw transactions and runs them as PoH batches on the
+              engine (fd_poh_gpu.h), fdgpu_poh_verify_host on the host.
 
    Both cut the work into batches within the verifier's limits, keep up to
    two batches in flight (the next one is staged while the GPU runs the
@@ -25,6 +31,7 @@
 #include <vector>
 
 #include "../../../include/fd_verify_tile.h"
+#include "../fdt_poh.h"
 #include "../fdt_shred.h"
 
 namespace {
@@ -233,6 +240,151 @@ int fdgpu_shreds_verify(fdgpu_verifier_t v, const uint8_t *arena, uint64_t arena
   }
   if (!r) r = p.submit(*c);
   if (!r) r = p.finish();
+  return r;
+}
+
+int fdgpu_poh_verify_host(const uint8_t *arena, uint64_t arena_sz, const fdgpu_poh_entry_t *entries, uint64_t n,
+                          const uint32_t *sig_offs, uint64_t sig_total, uint64_t hash_cnt_cap, int8_t *codes,
+                          uint8_t *hashes) {
+  if (!codes || (!arena && arena_sz) || (!entries && n) || (!sig_offs && sig_total)) return FDGPU_ERR_INVAL;
+  uint64_t bad;
+  if (fdt_poh_args(arena_sz, entries, n, sig_offs, sig_total, hash_cnt_cap, &bad)) return FDGPU_ERR_INVAL;
+  /* entries dealt to the threads one at a time: their lengths differ by orders of magnitude */
+  std::atomic<uint64_t> next{0};
+  auto work = [&] {
+    std::vector<uint8_t> nodes;
+    uint8_t out[32];
+    for (uint64_t i; (i = next.fetch_add(1)) < n;) {
+      nodes.resize(32 * std::max<uint64_t>(entries[i].sig_cnt, 1));
+      codes[i] = (int8_t)fdt_poh_entry(arena, entries + i, sig_offs, hash_cnt_cap, nodes.data(), out);
+      if (hashes) memcpy(hashes + 32 * i, out, 32);
+    }
+  };
+  const unsigned hw = std::thread::hardware_concurrency();
+  const uint64_t nt = std::min<uint64_t>({16, hw ? hw : 1, n});
+  std::vector<std::thread> th;
+  for (uint64_t t = 1; t < nt; t++) th.emplace_back(work);
+  work();
+  for (auto &t : th) t.join();
+  return FDGPU_OK;
+}
+
+int fdgpu_block_poh_verify(fdgpu_engine_t *e, const uint8_t in_hash[32], const uint64_t *hash_cnt, const uint8_t *entry_hash,
+                           const uint32_t *txn_cnt, uint64_t m, const uint8_t *payloads, const uint64_t *off,
+                           const uint32_t *sz, uint64_t n_txn, uint64_t hash_cnt_cap, uint64_t batch_entry_max,
+                           int8_t *codes) {
+  if (!codes || !batch_entry_max || (m && (!in_hash || !hash_cnt || !entry_hash || !txn_cnt)) ||
+      (n_txn && (!payloads || !off || !sz)) || hash_cnt_cap < 1 || hash_cnt_cap > FDGPU_POH_HASH_CNT_MAX)
+    return FDGPU_ERR_INVAL;
+  uint64_t tot = 0;
+  for (uint64_t i = 0; i < m; i++) tot += txn_cnt[i];
+  if (tot != n_txn) return FDGPU_ERR_INVAL;
+  uint64_t entry_max = batch_entry_max, sig_max = UINT32_MAX, arena_max = UINT32_MAX - 64ull * 1024;
+  if (e) {
+    uint64_t em = 0;
+    if (fdgpu_poh_limits(e, &em, &sig_max, &arena_max)) return FDGPU_ERR_INVAL;
+    entry_max = std::min(entry_max, em);
+  }
+  /* a batch: per entry its start hash, its claimed hash and its signatures, copied into an arena of the batch's own */
+  struct PohChunk {
+    std::vector<uint8_t> arena;
+    std::vector<fdgpu_poh_entry_t> en;
+    std::vector<uint32_t> so;
+    std::vector<uint64_t> items;   /* caller's index of each entry */
+    int64_t ticket = -1;
+  } slot[2];
+  int head = 0, cnt = 0;
+  std::vector<int8_t> buf;
+  auto drain_one = [&]() -> int {
+    PohChunk &c = slot[head];
+    buf.resize(std::max<size_t>(c.en.size(), 1));
+    const int r = fdgpu_poll_poh(e, c.ticket, buf.data(), nullptr, 1);
+    if (r != FDGPU_OK) return r < 0 ? r : FDGPU_ERR_DEVICE;
+    for (size_t i = 0; i < c.items.size(); i++) codes[c.items[i]] = buf[i];
+    head ^= 1;
+    cnt--;
+    return 0;
+  };
+  auto next = [&](PohChunk **out) -> int {     /* the chunk to fill next (drains the oldest when both are busy) */
+    if (cnt == 2) {
+      const int r = drain_one();
+      if (r) return r;
+    }
+    PohChunk &c = slot[(head + cnt) & 1];
+    c.arena.clear(); c.en.clear(); c.so.clear(); c.items.clear();
+    *out = &c;
+    return 0;
+  };
+  auto submit = [&](PohChunk &c) -> int {
+    if (c.en.empty()) return 0;
+    if (!e) {
+      buf.resize(c.en.size());
+      const int r = fdgpu_poh_verify_host(c.arena.data(), c.arena.size(), c.en.data(), c.en.size(), c.so.data(),
+                                          c.so.size(), hash_cnt_cap, buf.data(), nullptr);
+      if (r) return r;
+      for (size_t i = 0; i < c.items.size(); i++) codes[c.items[i]] = buf[i];
+      return 0;
+    }
+    int64_t tk;
+    while ((tk = fdgpu_submit_poh(e, c.arena.data(), c.arena.size(), c.en.data(), c.en.size(), c.so.data(), c.so.size(),
+                                  hash_cnt_cap)) == FDGPU_ERR_FULL) {
+      if (!cnt) return FDGPU_ERR_FULL;
+      const int r = drain_one();
+      if (r) return r;
+    }
+    if (tk < 0) return (int)tk;
+    c.ticket = tk;
+    cnt++;
+    return 0;
+  };
+  alignas(8) uint8_t txn_buf[FDT_TXN_MAX_SZ];
+  std::vector<uint64_t> sig_at;                /* an entry's signatures: where they lie in payloads */
+  PohChunk *c = nullptr;
+  int r = next(&c);
+  uint64_t t = 0;
+  for (uint64_t i = 0; i < m && !r; t += txn_cnt[i], i++) {
+    bool parsed = true;
+    sig_at.clear();
+    for (uint64_t j = t; j < t + txn_cnt[i] && parsed; j++) {
+      const uint8_t *raw = payloads + off[j];
+      const uint64_t psz = std::min<uint64_t>(sz[j], FDT_TXN_MTU);
+      if (!fdt_txn_parse(raw, psz, txn_buf, nullptr)) { parsed = false; break; }
+      const fdt_txn_t *tx = (const fdt_txn_t *)txn_buf;
+      for (uint64_t k = 0; k < tx->signature_cnt; k++) sig_at.push_back(off[j] + tx->signature_off + 64 * k);
+    }
+    if (!parsed) { codes[i] = FDGPU_REPLAY_PARSE_FAIL; continue; }
+    const uint64_t need = 64 + 64 * sig_at.size();
+    if (sig_at.size() > sig_max || need > arena_max) { r = FDGPU_ERR_INVAL; break; }   /* one entry no batch can hold */
+    if (c->en.size() == entry_max || c->so.size() + sig_at.size() > sig_max || c->arena.size() + need > arena_max) {
+      r = submit(*c);
+      if (!r) r = next(&c);
+      if (r) break;
+    }
+    /* item = start hash[32] | claimed hash[32] | its signatures[64 each] */
+    const uint32_t base = (uint32_t)c->arena.size();
+    const uint8_t *prev = i ? entry_hash + 32 * (i - 1) : in_hash;
+    c->arena.insert(c->arena.end(), prev, prev + 32);
+    c->arena.insert(c->arena.end(), entry_hash + 32 * i, entry_hash + 32 * i + 32);
+    fdgpu_poh_entry_t d;
+    d.hash_cnt = hash_cnt[i];
+    d.prev_off = base;
+    d.hash_off = base + 32;
+    d.sig_first = (uint32_t)c->so.size();
+    d.sig_cnt = (uint32_t)sig_at.size();
+    d.mix_off = FDGPU_POH_NO_MIX;
+    d._pad = 0;
+    for (uint64_t at : sig_at) {
+      c->so.push_back((uint32_t)c->arena.size());
+      c->arena.insert(c->arena.end(), payloads + at, payloads + at + 64);
+    }
+    c->en.push_back(d);
+    c->items.push_back(i);
+  }
+  if (!r) r = submit(*c);
+  while (cnt) {                                /* on an error too: no batch is left in the ring */
+    const int d = drain_one();
+    if (d) return r ? r : d;
+  }
   return r;
 }
 

@@ -39,6 +39,24 @@ ARENA_SLACK = 160
 SHRED_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("pub_off", "<u4")])   # fdgpu_shred_t
 CODE_SHRED_REJECT = -67       # FDGPU_CODE_SHRED_REJECT
 SHRED_SZ_MAX = 1228 + 4       # FDGPU_SHRED_SZ_MAX
+# fdgpu_poh_entry_t (include/fd_poh_gpu.h)
+POH_DTYPE = np.dtype([("hash_cnt", "<u8"), ("prev_off", "<u4"), ("hash_off", "<u4"), ("sig_first", "<u4"),
+                      ("sig_cnt", "<u4"), ("mix_off", "<u4"), ("_pad", "<u4")])
+POH_NO_MIX = 0xFFFFFFFF       # FDGPU_POH_NO_MIX
+POH_HASH_CNT_MAX = 1 << 20    # FDGPU_POH_HASH_CNT_MAX
+CODE_POH_MISMATCH = -68       # FDGPU_CODE_POH_MISMATCH
+CODE_POH_TOO_LONG = -69       # FDGPU_CODE_POH_TOO_LONG
+
+
+def poh_chunk():
+    """fdgpu_poh_chunk: hashes a lane of the chain kernel runs between two
+    looks at the entry queue."""
+    return int(_lib.lib().fdgpu_poh_chunk())
+
+
+def _poh_arrays(arena, entries, sig_offs):
+    return (np.ascontiguousarray(arena, dtype=np.uint8), np.ascontiguousarray(entries, dtype=POH_DTYPE),
+            np.ascontiguousarray(sig_offs, dtype=np.uint32))
 
 
 def verify(msg, sig, public_key, sha=None):
@@ -282,6 +300,34 @@ class VerifyEngine:
     def verify_shreds(self, arena, shreds, expected_version):
         return self.poll_shreds(self.submit_shreds(arena, shreds, expected_version), blocking=True)
 
+    def submit_poh(self, arena, entries, sig_offs, hash_cnt_cap):
+        """fdgpu_submit_poh: a block's PoH entries (POH_DTYPE; sig_offs: the
+        arena offsets of their signatures) hashed, rooted, mixed and compared
+        on the GPU."""
+        arena, entries, sig_offs = _poh_arrays(arena, entries, sig_offs)
+        tk = _lib.lib().fdgpu_submit_poh(self._h, arena.ctypes.data, arena.size, entries.ctypes.data, len(entries),
+                                         sig_offs.ctypes.data, len(sig_offs), int(hash_cnt_cap))
+        if tk < 0:
+            raise RuntimeError(f"fdgpu_submit_poh failed ({tk}): {_lib.last_error()}")
+        self._pending[tk] = len(entries)
+        return tk
+
+    def poll_poh(self, ticket, blocking=True):
+        """-> (codes int8[n], hashes uint8[n, 32]) or None while pending."""
+        n = self._pending[ticket]
+        codes = np.zeros(max(n, 1), dtype=np.int8)
+        hashes = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        rc = _lib.lib().fdgpu_poll_poh(self._h, ticket, codes.ctypes.data, hashes.ctypes.data, 1 if blocking else 0)
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise RuntimeError(f"fdgpu_poll_poh failed ({rc}): {_lib.last_error()}")
+        del self._pending[ticket]
+        return codes[:n], hashes[:n]
+
+    def verify_poh(self, arena, entries, sig_offs, hash_cnt_cap):
+        return self.poll_poh(self.submit_poh(arena, entries, sig_offs, hash_cnt_cap), blocking=True)
+
     def verify_device(self, d_arena, d_sig_desc, n_sig, d_txn_desc, n_txn, d_sig_codes, d_txn_codes, stream=0):
         """Device-resident path; all pointers are device addresses (ints)."""
         rc = _lib.lib().fdgpu_verify_device(self._h, d_arena, d_sig_desc, n_sig, d_txn_desc, n_txn,
@@ -360,6 +406,27 @@ class VerifyEngine:
                                                     len(shreds), int(expected_version), int(iters), ctypes.byref(a),
                                                     ctypes.byref(v)), "debug_shred_time")
         return a.value, v.value
+
+    def debug_poh(self, arena, entries, sig_offs, hash_cnt_cap, grid_waves=0):
+        """The PoH pipeline outside the ring, the chain kernel's grid forced
+        to grid_waves waves (0: the default) -> (codes int8[n], hashes uint8[n, 32])"""
+        arena, entries, sig_offs = _poh_arrays(arena, entries, sig_offs)
+        codes = np.zeros(len(entries), dtype=np.int8)
+        hashes = np.zeros((len(entries), 32), dtype=np.uint8)
+        self._chk(_lib.lib().fdgpu_debug_poh(self._h, arena.ctypes.data, arena.size, entries.ctypes.data, len(entries),
+                                             sig_offs.ctypes.data, len(sig_offs), int(hash_cnt_cap), int(grid_waves),
+                                             codes.ctypes.data, hashes.ctypes.data), "debug_poh")
+        return codes, hashes
+
+    def debug_poh_time(self, arena, entries, sig_offs, hash_cnt_cap, iters=5):
+        """-> (tree_ms, chain_ms): mean device time of the batch's leaves and
+        roots and of its chains, the batch resident in HBM"""
+        arena, entries, sig_offs = _poh_arrays(arena, entries, sig_offs)
+        t, ch = ctypes.c_double(), ctypes.c_double()
+        self._chk(_lib.lib().fdgpu_debug_poh_time(self._h, arena.ctypes.data, arena.size, entries.ctypes.data,
+                                                  len(entries), sig_offs.ctypes.data, len(sig_offs), int(hash_cnt_cap),
+                                                  int(iters), ctypes.byref(t), ctypes.byref(ch)), "debug_poh_time")
+        return t.value, ch.value
 
     def debug_hram(self, arena, txns):
         arena = np.ascontiguousarray(arena, dtype=np.uint8)

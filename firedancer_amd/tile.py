@@ -23,7 +23,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .ed25519 import TXN_DTYPE
+from .ed25519 import CODE_POH_MISMATCH, CODE_POH_TOO_LONG, POH_DTYPE, POH_NO_MIX, TXN_DTYPE  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 TILE_LIB_PATH = os.environ.get("FDGPU_TILE_LIB") or os.path.join(_HERE, "libfd_verify_tile.so")
@@ -291,6 +291,8 @@ def lib():
         "fdgpu_replay_verify": (c.c_int, [Verifier, vp, vp, vp, u64, u64, u64, vp]),
         "fdgpu_fec_roots_verify": (c.c_int, [Verifier, vp, vp, vp, c.c_int, u64, u64, vp]),
         "fdgpu_shreds_verify": (c.c_int, [Verifier, vp, u64, vp, u64, c.c_uint16, u64, vp, vp]),
+        "fdgpu_poh_verify_host": (c.c_int, [vp, u64, vp, u64, vp, u64, u64, vp, vp]),
+        "fdgpu_block_poh_verify": (c.c_int, [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, u64, u64, vp]),
         "fdt_shred_check": (c.c_int, [vp, u64, c.c_uint16, c.POINTER(ShredChk)]),
         "fdt_shred_root": (None, [vp, c.POINTER(ShredChk), vp]),
         "fdt_sha256": (None, [vp, u64, vp]),
@@ -1093,6 +1095,48 @@ def shreds_verify(verifier, arena, shreds, expected_version, batch_max=65536):
     if r:
         raise RuntimeError(f"fdgpu_shreds_verify failed: {r}")
     return codes[:n], roots[:n]
+
+
+def poh_verify_host(arena, entries, sig_offs, hash_cnt_cap):
+    """A PoH batch on the host (fdgpu_poh_verify_host), the CPU path of
+    VerifyEngine.verify_poh -> (codes int8[n], hashes uint8[n, 32])"""
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    entries = np.ascontiguousarray(entries, dtype=POH_DTYPE)
+    sig_offs = np.ascontiguousarray(sig_offs, dtype=np.uint32)
+    n = len(entries)
+    codes = np.zeros(max(n, 1), dtype=np.int8)
+    hashes = np.zeros((max(n, 1), 32), dtype=np.uint8)
+    r = lib().fdgpu_poh_verify_host(arena.ctypes.data, arena.size, entries.ctypes.data, n, sig_offs.ctypes.data,
+                                    len(sig_offs), int(hash_cnt_cap), codes.ctypes.data, hashes.ctypes.data)
+    if r:
+        raise RuntimeError(f"fdgpu_poh_verify_host failed: {r}")
+    return codes[:n], hashes[:n]
+
+
+def block_poh_verify(engine, in_hash, hash_cnt, entry_hash, txn_cnt, payloads, hash_cnt_cap, batch_entry_max=65536):
+    """fdgpu_block_poh_verify: the entries of one or many blocks in order
+    (hash_cnt[i], the 32 bytes entry_hash[i] claims, txn_cnt[i]) and their raw
+    transactions (a list of bytes, entry 0's first).  engine: a VerifyEngine,
+    or None for the host path -> codes int8[m]"""
+    hash_cnt = np.ascontiguousarray(hash_cnt, dtype=np.uint64)
+    txn_cnt = np.ascontiguousarray(txn_cnt, dtype=np.uint32)
+    m = len(hash_cnt)
+    eh = np.ascontiguousarray(np.frombuffer(b"".join(bytes(h) for h in entry_hash) + b"\0", dtype=np.uint8))
+    if len(txn_cnt) != m or len(eh) != 32 * m + 1 or len(bytes(in_hash)) != 32:
+        raise ValueError("hash_cnt/entry_hash/txn_cnt sizes disagree")
+    n = len(payloads)
+    sizes = np.array([len(p) for p in payloads], dtype=np.uint32)
+    offs = np.zeros(max(n, 1), dtype=np.uint64)
+    if n:
+        offs[1:n] = np.cumsum(sizes[:-1], dtype=np.uint64)
+    arena = np.frombuffer(b"".join(payloads) + b"\0", dtype=np.uint8)
+    codes = np.zeros(max(m, 1), dtype=np.int8)
+    r = lib().fdgpu_block_poh_verify(engine._h if engine is not None else None, bytes(in_hash), hash_cnt.ctypes.data,
+                                     eh.ctypes.data, txn_cnt.ctypes.data, m, arena.ctypes.data, offs.ctypes.data,
+                                     sizes.ctypes.data, n, int(hash_cnt_cap), int(batch_entry_max), codes.ctypes.data)
+    if r:
+        raise RuntimeError(f"fdgpu_block_poh_verify failed: {r}")
+    return codes[:m]
 
 
 # ------------------------------------------------------------------ tiles
