@@ -86,6 +86,42 @@ int fdgpu_debug_hs_split(fdgpu_engine_t *e, uint8_t const *k, uint64_t n, uint8_
   return debug_map(e, k, n, 8, 16, out, fdgpu_launch_test_hs_split);
 }
 
+int fdgpu_debug_fe_raw(fdgpu_engine_t *e, uint8_t const *fg, uint64_t n, uint8_t *out) {
+  return debug_map(e, fg, n, 20, 80, out, fdgpu_launch_test_fe_raw);
+}
+
+int fdgpu_debug_ge_ops(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint8_t *out) {
+  return debug_map(e, in, n, fdgpu_test_ge_in_words(), 32u * fdgpu_test_ge_results(), out, fdgpu_launch_test_ge);
+}
+
+int fdgpu_debug_sc_recode(fdgpu_engine_t *e, uint8_t const *s, uint64_t n, uint8_t *out) {
+  return debug_map(e, s, n, 8, 16, out, fdgpu_launch_test_sc_recode);
+}
+
+int fdgpu_debug_btab(fdgpu_engine_t *e, uint64_t first_entry, uint64_t n_entries, uint32_t *out) {
+  const uint64_t total = (uint64_t)FDGPU_BCOMB_NDIG * FDGPU_BCOMB_ENTRIES;
+  if (!e || !e->d_btab || !out || first_entry > total || n_entries > total - first_entry) {
+    set_err("fdgpu_debug_btab: entries out of the table"); return FDGPU_ERR_INVAL;
+  }
+  if (!n_entries) return FDGPU_OK;
+  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
+  HIPCHK(hipStreamSynchronize(e->compute), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(out, e->d_btab + first_entry * FDGPU_BCOMB_STRIDE, n_entries * FDGPU_BCOMB_STRIDE * sizeof(uint32_t),
+                   hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
+  return FDGPU_OK;
+}
+
+uint32_t fdgpu_bcomb_dim(int which) {
+  switch (which) {
+    case 0: return FDGPU_BCOMB_BITS;
+    case 1: return FDGPU_BCOMB_NDIG;
+    case 2: return FDGPU_BCOMB_ENTRIES;
+    case 3: return FDGPU_BCOMB_STRIDE;
+    case 4: return FDGPU_BCOMB_CHUNK;
+    default: return 0u;
+  }
+}
+
 int fdgpu_debug_sig_codes(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *txns,
                           uint64_t txn_cnt, int8_t *sig_codes) {
   if (!e) return FDGPU_ERR_INVAL;

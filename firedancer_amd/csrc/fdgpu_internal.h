@@ -293,6 +293,25 @@ hipError_t fdgpu_launch_test_hram(const uint8_t *d_arena, const fdgpu_sig_desc_t
                                   uint32_t *d_out, hipStream_t stream);
 hipError_t fdgpu_launch_test_sc_reduce(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
 hipError_t fdgpu_launch_test_hs_split(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
+/* the group layer (tests/test_gpu_group.py): field ops on raw limbs (20 u32 in, 80 out), every group
+   operation on a pair of points (fdgpu_test_ge_in_words() in, 32 x fdgpu_test_ge_results() out), and the
+   two scalar recodings (8 in, 16 out) */
+hipError_t fdgpu_launch_test_fe_raw(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
+uint32_t   fdgpu_test_ge_in_words(void);
+uint32_t   fdgpu_test_ge_results(void);
+hipError_t fdgpu_launch_test_ge(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
+hipError_t fdgpu_launch_test_sc_recode(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
+
+/* ---- fdgpu_diag.cpp: the group layer's diagnostics, exported for the parity tests beside the
+   fdgpu_debug_* of include/fd_ed25519_gpu.h (same conventions: synchronous, 0 on success) ---- */
+int      fdgpu_debug_fe_raw(fdgpu_engine_t *e, uint8_t const *fg, uint64_t n, uint8_t *out);
+int      fdgpu_debug_ge_ops(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint8_t *out);
+int      fdgpu_debug_sc_recode(fdgpu_engine_t *e, uint8_t const *s, uint64_t n, uint8_t *out);
+/* n_entries x FDGPU_BCOMB_STRIDE words of the engine's fixed-base table, from entry first_entry of the
+   flat (table, entry) order, to the host; no kernel runs */
+int      fdgpu_debug_btab(fdgpu_engine_t *e, uint64_t first_entry, uint64_t n_entries, uint32_t *out);
+/* the comb's shape: which = 0 W, 1 NDIG, 2 entries per table, 3 words per entry, 4 entries per fill chunk */
+uint32_t fdgpu_bcomb_dim(int which);
 
 #ifdef __cplusplus
 }

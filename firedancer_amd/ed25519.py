@@ -54,6 +54,19 @@ def poh_chunk():
     return int(_lib.lib().fdgpu_poh_chunk())
 
 
+def bcomb_dims():
+    """fdgpu_bcomb_dim: the fixed-base comb's shape: radix bits, tables,
+    entries per table, u32 per entry, entries per chunk of the table build."""
+    L = _lib.lib()
+    return {k: int(L.fdgpu_bcomb_dim(i)) for i, k in enumerate(("w", "ndig", "entries", "stride", "chunk"))}
+
+
+def ge_ops_shape():
+    """(u32 per input record, results per record) of debug_ge_ops."""
+    L = _lib.lib()
+    return int(L.fdgpu_test_ge_in_words()), int(L.fdgpu_test_ge_results())
+
+
 def _poh_arrays(arena, entries, sig_offs):
     return (np.ascontiguousarray(arena, dtype=np.uint8), np.ascontiguousarray(entries, dtype=POH_DTYPE),
             np.ascontiguousarray(sig_offs, dtype=np.uint32))
@@ -447,6 +460,40 @@ class VerifyEngine:
         k = np.ascontiguousarray(k, dtype=np.uint8).reshape(-1, 32)
         out = np.zeros((len(k), 16), dtype=np.uint32)
         self._chk(_lib.lib().fdgpu_debug_hs_split(self._h, k.ctypes.data, len(k), out.ctypes.data), "debug_hs_split")
+        return out
+
+    def debug_fe_raw(self, fg):
+        """fg: uint32[n, 20] raw limb vectors (f, g), taken as they are ->
+        uint32[n, 10, 8] canonical LE words of f*g, f^2, f+g, f-g, (f-g)*g,
+        -f, (-f)*g, f, f-g by 4p, (f-g by 4p)*g"""
+        fg = np.ascontiguousarray(fg, dtype=np.uint32).reshape(-1, 20)
+        out = np.zeros((len(fg), 10, 8), dtype=np.uint32)
+        self._chk(_lib.lib().fdgpu_debug_fe_raw(self._h, fg.ctypes.data, len(fg), out.ctypes.data), "debug_fe_raw")
+        return out
+
+    def debug_ge_ops(self, rec):
+        """rec: uint32[n, ge_ops_shape()[0]]: P and Q (X, Y, Z, T as 8 LE
+        words each) and Q's affine niels form -> uint32[n, results, 4, 8]
+        (X, Y, Z, T canonical; the results' order: csrc/fdgpu_test_kernels.hip)"""
+        w_in, n_res = ge_ops_shape()
+        rec = np.ascontiguousarray(rec, dtype=np.uint32).reshape(-1, w_in)
+        out = np.zeros((len(rec), n_res, 4, 8), dtype=np.uint32)
+        self._chk(_lib.lib().fdgpu_debug_ge_ops(self._h, rec.ctypes.data, len(rec), out.ctypes.data), "debug_ge_ops")
+        return out
+
+    def debug_sc_recode(self, s):
+        """s: uint8[n, 32] scalars -> uint32[n, 16]: sc_recode16's packed
+        digits (8 words), then the comb recoding's"""
+        s = np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 32)
+        out = np.zeros((len(s), 16), dtype=np.uint32)
+        self._chk(_lib.lib().fdgpu_debug_sc_recode(self._h, s.ctypes.data, len(s), out.ctypes.data), "debug_sc_recode")
+        return out
+
+    def debug_btab(self):
+        """The engine's fixed-base comb table -> uint32[NDIG, entries, stride]"""
+        d = bcomb_dims()
+        out = np.zeros((d["ndig"], d["entries"], d["stride"]), dtype=np.uint32)
+        self._chk(_lib.lib().fdgpu_debug_btab(self._h, 0, d["ndig"] * d["entries"], out.ctypes.data), "debug_btab")
         return out
 
     def debug_sig_codes(self, arena, txns):

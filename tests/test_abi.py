@@ -34,6 +34,20 @@ def test_dynamic_symbol_table_lists_exports():
         assert n in syms, n
 
 
+def test_group_diagnostics_are_exported():
+    """The group layer's diagnostics (declared in csrc/fdgpu_internal.h, bound
+    by _lib.lib() for tests/test_gpu_group.py) are dynamic symbols, and the
+    comb's shape is readable without a GPU."""
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    syms = set(re.findall(r"\s[TW]\s(\w+)$", out, flags=re.M))
+    for n in ("fdgpu_debug_fe_raw", "fdgpu_debug_ge_ops", "fdgpu_debug_sc_recode", "fdgpu_debug_btab",
+              "fdgpu_bcomb_dim"):
+        assert n in syms, n
+    from firedancer_amd import ed25519 as ed
+    assert ed.bcomb_dims() == {"w": 16, "ndig": 16, "entries": 32769, "stride": 32, "chunk": 64}
+    assert ed.ge_ops_shape() == (88, 21)
+
+
 def test_engine_internals_are_not_exported():
     """The engine's units share their internals through namespace fdgpu
     (csrc/fdgpu_engine.h, hidden visibility): none of them is a dynamic
