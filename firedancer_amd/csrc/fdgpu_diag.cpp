@@ -98,6 +98,10 @@ int fdgpu_debug_sc_recode(fdgpu_engine_t *e, uint8_t const *s, uint64_t n, uint8
   return debug_map(e, s, n, 8, 16, out, fdgpu_launch_test_sc_recode);
 }
 
+int fdgpu_debug_tabpack(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint8_t *out) {
+  return debug_map(e, in, n, FDGPU_ATAB_WORDS, FDGPU_TABPACK_OUT_WORDS, out, fdgpu_launch_test_tabpack);
+}
+
 int fdgpu_debug_btab(fdgpu_engine_t *e, uint64_t first_entry, uint64_t n_entries, uint32_t *out) {
   const uint64_t total = (uint64_t)FDGPU_BCOMB_NDIG * FDGPU_BCOMB_ENTRIES;
   if (!e || !e->d_btab || !out || first_entry > total || n_entries > total - first_entry) {

@@ -32,8 +32,10 @@ typedef struct {
 /* k in signed radix 16: 64 windows over the per-lane table {O, -A, .., -8A} */
 #define FDGPU_ATAB_ENTRIES  9u            /* 0 (identity), 1A .. 8A (A negated) */
 #ifndef FDGPU_ATAB_WORDS
-#define FDGPU_ATAB_WORDS    40u           /* u32 per cached entry (a diagnostic build may pad it) */
+#define FDGPU_ATAB_WORDS    40u           /* u32 per cached entry, unpacked (4 coordinates x 10 limbs) */
 #endif
+#define FDGPU_PTAB_WORDS    32u           /* u32 per stored table entry: 4 coordinates packed to 8 words, one 128-B line
+                                             (fdgpu_atab.h) */
 #ifndef FDGPU_VERIFY_WAVES
 #define FDGPU_VERIFY_WAVES  2             /* waves per SIMD of the verify kernel: decode/pow chains want ~190 VGPRs */
 #endif
@@ -58,28 +60,52 @@ typedef struct {
 #define FDGPU_BCOMB_ENTRIES ((1u << (FDGPU_BCOMB_BITS - 1u)) + 1u)
 #define FDGPU_BCOMB_STRIDE  32u           /* u32 per entry (30 used): one 128-B line */
 #define FDGPU_BCOMB_CHUNK   64u           /* entries per lane in the table build (one batch inversion) */
-/* The verify equation with half-size scalars (fdgpu_lattice.h).  Per-lane
-   workspace entries (cached form, 40 words each): */
+/* The verify equation with half-size scalars (fdgpu_lattice.h). */
 #define HS_MAX_WIN          40u           /* radix-16 windows of |u|, |v| (< 2^159) */
 /* A table's identity entry (digit 0) is one shared constant (g_tab_ident),
    so a lane stores entries 1..8 of each table */
 #define FDGPU_TAB_STORED    (FDGPU_ATAB_ENTRIES - 1u)
-                                          /* entries 0..7: 1..8 of the -A table */
-#define FDGPU_WS_RTAB       FDGPU_TAB_STORED            /* entries 8..15: 1..8 of the -R table */
-#define FDGPU_WS_PARK       (2u * FDGPU_TAB_STORED)     /* entry: k digits, decoded R, code (full path) */
-#define FDGPU_WS_SB         (FDGPU_WS_PARK + 1u)        /* entry: [w]B (or [S]B) in cached form */
-#define FDGPU_WS_ENTRIES    (FDGPU_WS_SB + 1u)          /* 18 entries: 2880 B per signature */
-#define FDGPU_WS_LANE_WORDS (FDGPU_WS_ENTRIES * FDGPU_ATAB_WORDS)
+/* The workspace holds FDGPU_WS_LANE_WORDS per lane (the size of 18 unpacked
+   entries, kept: fdgpu_ws_bytes is part of the ABI), laid out as two regions:
+     tables   lane i at word i * FDGPU_WS_TAB_WORDS: 16 packed entries, one
+              128-B line each (2 KiB, line-aligned) -- entries 0..7 are 1..8
+              of the -A table, 8..15 are 1..8 of the -R table;
+     aux      after every lane's tables, FDGPU_WS_AUX_WORDS per lane, counted
+              back from the region's end (where the fallback queue starts):
+              lane i at end - (i + 1) * FDGPU_WS_AUX_WORDS.  Plain words: the
+              park entry (k digits, code: the full path) at FDGPU_AUX_PARK and
+              [w]B (or [S]B), an unpacked cached entry in canonical order, at
+              FDGPU_AUX_SB; the rest of a lane's aux words is unused. */
+#define FDGPU_WS_RTAB       FDGPU_TAB_STORED
+#define FDGPU_WS_ENTRIES    (2u * FDGPU_TAB_STORED + 2u)                  /* 16 table entries, park, [w]B */
+#define FDGPU_WS_LANE_WORDS (FDGPU_WS_ENTRIES * FDGPU_ATAB_WORDS)         /* 720 */
+#define FDGPU_WS_TAB_WORDS  (2u * FDGPU_TAB_STORED * FDGPU_PTAB_WORDS)    /* 512 */
+#define FDGPU_WS_AUX_WORDS  (FDGPU_WS_LANE_WORDS - FDGPU_WS_TAB_WORDS)    /* 208 */
+#define FDGPU_AUX_PARK      0u
+#define FDGPU_AUX_SB        FDGPU_ATAB_WORDS
 #define FDGPU_BLOCK         256u
 #define FDGPU_FLAG_REF_MAP  1u            /* portable-backend error mapping */
 #define FDGPU_FLAG_KFULL    2u            /* half-size path: every lane takes the full-length fallback */
 #define FDGPU_FLAG_KCACHE   4u            /* half-size path: one -A decode + table per distinct key */
 #define FDGPU_FLAG_KPAIR    8u            /* half-size path, two lanes per signature (fdgpu_verify_pair_kernel) */
 #define FDGPU_FLAG_KSPREAD  16u           /* one verify block per CU: dynamic LDS that leaves no room for a second */
-/* the verify block's static LDS is 80 KB (two fill a CU's 160 KB), the
-   two-lane block's 40 KB: these make one block per CU the most that fits */
-#define FDGPU_SPREAD_LDS       1024u
-#define FDGPU_SPREAD_LDS_PAIR  (40u * 1024u + 1024u)
+/* The chain's LDS staging: one packed entry per lane and table, 8 chunks of
+   16 B x 64 lanes per wave.  The verify block stages two entries a window
+   (64 KB), the two-lane block one (32 KB).  FDGPU_FLAG_KSPREAD adds the
+   dynamic LDS that brings a block to just over half of a CU's 160 KB, so a
+   second block does not fit. */
+#define FDGPU_STAGE_WAVE_WORDS (FDGPU_PTAB_WORDS / 4u * 256u)
+#define FDGPU_STAGE_LDS        (FDGPU_BLOCK / 64u * 2u * FDGPU_STAGE_WAVE_WORDS * 4u)
+#define FDGPU_STAGE_LDS_PAIR   (FDGPU_BLOCK / 64u * FDGPU_STAGE_WAVE_WORDS * 4u)
+#define FDGPU_CU_LDS           (160u * 1024u)
+#define FDGPU_SPREAD_LDS       (FDGPU_CU_LDS / 2u - FDGPU_STAGE_LDS + 1024u)
+#define FDGPU_SPREAD_LDS_PAIR  (FDGPU_CU_LDS / 2u - FDGPU_STAGE_LDS_PAIR + 1024u)
+#ifdef __cplusplus
+static_assert(2u * (FDGPU_STAGE_LDS + FDGPU_SPREAD_LDS) > FDGPU_CU_LDS &&
+              2u * (FDGPU_STAGE_LDS_PAIR + FDGPU_SPREAD_LDS_PAIR) > FDGPU_CU_LDS &&
+              FDGPU_STAGE_LDS + FDGPU_SPREAD_LDS <= FDGPU_CU_LDS && FDGPU_STAGE_LDS_PAIR + FDGPU_SPREAD_LDS_PAIR <= FDGPU_CU_LDS,
+              "a spread launch's LDS admits one block per CU, and no more");
+#endif
 /* The verify blocks (two 256-VGPR waves per SIMD) fill every SIMD's register
    file, so a kernel queued behind or beside a running verify starts its
    workgroups only as verify blocks retire: a launch of many workgroups then
@@ -149,8 +175,11 @@ hipError_t fdgpu_launch_sha512_stream(const uint8_t *d_mbuf, uint64_t m0, uint64
 hipError_t fdgpu_launch_verify_prehashed(const uint8_t *d_arena, const fdgpu_sig_desc_t *d_sigs, uint32_t n_sig,
                                          const uint32_t *d_btab, uint32_t *d_ws, int8_t *d_sig_codes, uint32_t flags,
                                          hipStream_t stream);
-/* The verify workspace of an n_sig batch, in u32 words from d_ws: the lanes'
-   words (FDGPU_WS_LANE_WORDS each, lanes = n_sig rounded up to whole blocks),
+/* The verify workspace of an n_sig batch, in u32 words from d_ws (128-B
+   aligned): the lanes' words (FDGPU_WS_LANE_WORDS each, lanes = n_sig rounded
+   up to whole blocks: every lane's packed tables, FDGPU_WS_TAB_WORDS each,
+   then the lanes' aux words, which end where the queue starts -- the kernels
+   find a lane's aux words from the queue's address),
    the fallback queue (one word per lane), 16 words of counters (the queue's
    count, then the key cache's representative count), the key cache's hash
    table (ht_slots, a power of two >= 2 lanes and >= 64), then key_of,
@@ -301,12 +330,21 @@ uint32_t   fdgpu_test_ge_in_words(void);
 uint32_t   fdgpu_test_ge_results(void);
 hipError_t fdgpu_launch_test_ge(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
 hipError_t fdgpu_launch_test_sc_recode(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
+/* the packed table entry (tests/test_gpu_tabpack.py): a cached entry's 40 raw limbs in; per record
+   FDGPU_TABPACK_OUT_WORDS out (a multiple of a line: d_out must be 128-B aligned) -- the 32 words
+   atab_store leaves, then the 40 limbs of atab_load, of stage_entry + unstage_entry_signed, and of the
+   same with neg */
+#define FDGPU_TABPACK_OUT_WORDS 160u
+hipError_t fdgpu_launch_test_tabpack(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream);
 
 /* ---- fdgpu_diag.cpp: the group layer's diagnostics, exported for the parity tests beside the
    fdgpu_debug_* of include/fd_ed25519_gpu.h (same conventions: synchronous, 0 on success) ---- */
 int      fdgpu_debug_fe_raw(fdgpu_engine_t *e, uint8_t const *fg, uint64_t n, uint8_t *out);
 int      fdgpu_debug_ge_ops(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint8_t *out);
 int      fdgpu_debug_sc_recode(fdgpu_engine_t *e, uint8_t const *s, uint64_t n, uint8_t *out);
+/* n cached entries (40 u32 raw limbs each: Y+X, Y-X, 2Z, 2dT) through the table's store, load and LDS
+   path; FDGPU_TABPACK_OUT_WORDS u32 per entry out */
+int      fdgpu_debug_tabpack(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint8_t *out);
 /* n_entries x FDGPU_BCOMB_STRIDE words of the engine's fixed-base table, from entry first_entry of the
    flat (table, entry) order, to the host; no kernel runs */
 int      fdgpu_debug_btab(fdgpu_engine_t *e, uint64_t first_entry, uint64_t n_entries, uint32_t *out);

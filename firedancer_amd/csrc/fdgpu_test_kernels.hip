@@ -4,6 +4,7 @@
    result.  No batch uses them. */
 #include <hip/hip_runtime.h>
 
+#include "fdgpu_atab.h"
 #include "fdgpu_ge.h"
 #include "fdgpu_hram.h"
 #include "fdgpu_internal.h"
@@ -265,6 +266,39 @@ __global__ void __launch_bounds__(64) fdgpu_test_sc_recode_kernel(const uint32_t
   for (int j = 0; j < 8; j++) { w[j] = d16[j]; w[8 + j] = j < NW ? dc[j] : 0u; }
 }
 
+/* The packed table entry, one lane per record.  in: the 40 raw limbs of a
+   cached entry (Y+X, Y-X, 2Z, 2dT), taken as they are; out, per record
+   (FDGPU_TABPACK_OUT_WORDS, a whole number of lines): the 32 words atab_store
+   leaves at [0, 32) (as entry 1 of a table whose first stored entry is the
+   record's first line), the 40 limbs atab_load returns at [32, 72), those of
+   stage_entry + unstage_entry_signed at [72, 112), and of the same with neg
+   at [112, 152). */
+__global__ void __launch_bounds__(64) fdgpu_test_tabpack_kernel(const uint32_t *in, uint32_t *out, uint32_t n) {
+  __shared__ uint32_t s_stage[FDGPU_STAGE_WAVE_WORDS];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t *src = in + FDGPU_ATAB_WORDS * (size_t)i;
+  uint32_t *dst = out + FDGPU_TABPACK_OUT_WORDS * (size_t)i;
+  ge_cached c;
+#pragma unroll
+  for (int w = 0; w < 10; w++) { c.YpX.v[w] = src[w]; c.YmX.v[w] = src[10 + w]; c.Z2.v[w] = src[20 + w]; c.T2d.v[w] = src[30 + w]; }
+  uint32_t *tab = dst - FDGPU_PTAB_WORDS;       /* virtual base: entry 1 is the record's first line */
+  atab_store(tab, 1, c);
+  __threadfence();                              /* the entry is read back by this lane, also by LDS-DMA */
+  uint32_t q[40];
+  atab_load(q, tab, 1);
+#pragma unroll
+  for (int w = 0; w < 40; w++) dst[32 + w] = q[w];
+  stage_entry(s_stage, tab, 1);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  unstage_entry_signed(q, s_stage, false);
+#pragma unroll
+  for (int w = 0; w < 40; w++) dst[72 + w] = q[w];
+  unstage_entry_signed(q, s_stage, true);
+#pragma unroll
+  for (int w = 0; w < 40; w++) dst[112 + w] = q[w];
+}
+
 }  // namespace
 
 extern "C" {
@@ -308,6 +342,10 @@ hipError_t fdgpu_launch_test_ge(const uint32_t *d_in, uint32_t *d_out, uint32_t 
 }
 hipError_t fdgpu_launch_test_sc_recode(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream) {
   hipLaunchKernelGGL(fdgpu_test_sc_recode_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, d_in, d_out, n);
+  return hipGetLastError();
+}
+hipError_t fdgpu_launch_test_tabpack(const uint32_t *d_in, uint32_t *d_out, uint32_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(fdgpu_test_tabpack_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, d_in, d_out, n);
   return hipGetLastError();
 }
 

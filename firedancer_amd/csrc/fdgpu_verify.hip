@@ -24,6 +24,7 @@
    (fdgpu_shred.hip). */
 #include <hip/hip_runtime.h>
 
+#include "fdgpu_atab.h"
 #include "fdgpu_bcomb.h"
 #include "fdgpu_ge.h"
 #include "fdgpu_hram.h"
@@ -38,68 +39,40 @@ using namespace fdgpu;
 namespace {
 
 /* ---- per-lane tables in the global workspace ----
-   layout: lane-contiguous, ws[i * FDGPU_WS_LANE_WORDS + entry * 40 + word]
-   for signature i: a lane's entry is 160 contiguous bytes (32-B aligned),
-   read whole with ten 16-B loads, so a wave's table read touches ~2 cache
-   lines per lane and uses every byte it fetches (fdgpu_internal.h lists the
-   entries). */
+   lane i's 16 stored entries (1..8 of its -A table, then 1..8 of its -R
+   table) are the 2 KiB at ws + i * FDGPU_WS_TAB_WORDS, each a packed entry
+   of one 128-B line (fdgpu_atab.h: atab_store / atab_load and the LDS path
+   convert, every other reader sees canonical-order limbs); its park entry
+   and [w]B are plain words in the aux region behind the tables
+   (fdgpu_internal.h). */
 
-/* Stored word order of a cached entry: Y+X and Y-X
-   interleaved by pairs in the first five 16-B chunks -- chunk k = (Y+X
-   limbs 2k, 2k+1, Y-X limbs 2k, 2k+1) -- then 2Z and 2dT as they are.  A
-   chain addition of -P reads Y+X and Y-X swapped: with pairs the swap is a
-   per-lane 8-B offset of two ds_read_b64 (unstage_entry_signed) instead of
-   20 per-word selects.  atab_store / atab_load convert, so every other
-   reader sees the canonical order (Y+X, Y-X, 2Z, 2dT). */
-__host__ __device__ constexpr int atab_pos(int w) {
-  return w >= 20 ? w : w < 10 ? 4 * (w / 2) + (w % 2) : 4 * ((w - 10) / 2) + 2 + (w % 2);
-}
-
-/* A table's entry 0 -- the identity in cached form (Y+X = Y-X = 1, 2Z = 2,
-   2dT = 0) in the stored word order -- is this one constant for every lane
-   and table: digit-0 lookups read it (an L2 hit), and a lane's workspace
-   holds only entries 1..8 of its tables (2880 B per signature instead of
-   3200, a smaller footprint in the caches the table reads hit). */
-struct alignas(16) tab_ident_t { uint32_t w[FDGPU_ATAB_WORDS]; };
-__device__ const tab_ident_t g_tab_ident = {{1u, 0u, 1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 2u}};
-static_assert(atab_pos(0) == 0 && atab_pos(10) == 2 && atab_pos(20) == 20, "identity entry's stored order");
-
-/* Entry |e| of a table whose (virtual) base is `tab` (entry k at tab + 40 k
-   for k >= 1; see tab_a / tab_r): the shared identity for e == 0. */
-FDG_DEV const uint32_t *tab_entry(const uint32_t *tab, int e) {
-  return e ? tab + (uint32_t)(e < 0 ? -e : e) * FDGPU_ATAB_WORDS : g_tab_ident.w;
-}
 /* virtual bases of a lane's -A and -R tables: stored entry 1 sits at the
    table's first workspace entry */
-FDG_DEV uint32_t *tab_a(uint32_t *wsl) { return wsl - FDGPU_ATAB_WORDS; }
-FDG_DEV const uint32_t *tab_a(const uint32_t *wsl) { return wsl - FDGPU_ATAB_WORDS; }
-FDG_DEV uint32_t *tab_r(uint32_t *wsl) { return wsl + (FDGPU_WS_RTAB - 1u) * FDGPU_ATAB_WORDS; }
+FDG_DEV uint32_t *tab_a(uint32_t *wsl) { return wsl - FDGPU_PTAB_WORDS; }
+FDG_DEV const uint32_t *tab_a(const uint32_t *wsl) { return wsl - FDGPU_PTAB_WORDS; }
+FDG_DEV uint32_t *tab_r(uint32_t *wsl) { return wsl + (FDGPU_WS_RTAB - 1u) * FDGPU_PTAB_WORDS; }
 
-FDG_DEV void atab_store(uint32_t *wsl, uint32_t entry, const ge_cached &c) {
-  uint4 *p = (uint4 *)(wsl + entry * FDGPU_ATAB_WORDS);
-  uint32_t w[40], o[40];
+/* [w]B (or [S]B) of a lane: an unpacked cached entry in canonical order at
+   the lane's aux words (written once and read once per signature) */
+FDG_DEV void sb_store(uint32_t *aux, const ge_cached &c) {
+  uint4 *p = (uint4 *)(aux + FDGPU_AUX_SB);
+  uint32_t w[40];
 #pragma unroll
   for (int i = 0; i < 10; i++) { w[i] = c.YpX.v[i]; w[10 + i] = c.YmX.v[i]; w[20 + i] = c.Z2.v[i]; w[30 + i] = c.T2d.v[i]; }
 #pragma unroll
-  for (int i = 0; i < 40; i++) o[atab_pos(i)] = w[i];
+  for (int q = 0; q < 10; q++) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+}
+FDG_DEV void sb_load(uint32_t (&q)[40], const uint32_t *aux) {
+  const uint4 *ent = (const uint4 *)(aux + FDGPU_AUX_SB);
 #pragma unroll
-  for (int q = 0; q < 10; q++) p[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+  for (int i = 0; i < 10; i++) {
+    const uint4 v = ent[i];
+    q[4 * i] = v.x; q[4 * i + 1] = v.y; q[4 * i + 2] = v.z; q[4 * i + 3] = v.w;
+  }
 }
 FDG_DEV int sext4(uint32_t x) { return ((int)(x << 28)) >> 28; }
 
 #define KD_WORDS 8        /* 64 signed radix-16 digits of k, one per nibble */
-
-FDG_DEV void atab_load(uint32_t (&q)[40], const uint32_t *wsl, int e) {
-  const uint4 *ent = (const uint4 *)tab_entry(wsl, e);
-  uint32_t o[40];
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    const uint4 v = ent[i];
-    o[4 * i] = v.x; o[4 * i + 1] = v.y; o[4 * i + 2] = v.z; o[4 * i + 3] = v.w;
-  }
-#pragma unroll
-  for (int i = 0; i < 40; i++) q[i] = o[atab_pos(i)];
-}
 
 /* shift a 256-bit little-endian word vector left by 4 bits */
 FDG_DEV void shl4(uint32_t (&w)[8]) {
@@ -109,12 +82,11 @@ FDG_DEV void shl4(uint32_t (&w)[8]) {
 }
 
 /* R' = [k](-A) + [S]B with [S]B precomputed by the
-   comb in pass 1 and parked (cached form) in workspace entry 10.  The chain
+   comb in pass 1 and parked (cached form) in the lane's aux words.  The chain
    only serves k: 64 windows of 4 doublings + one A-table addition; the last
    window's sum is converted to p3 and the parked [S]B added. */
-FDG_DEV void dsm_k(ge_p2 &acc2, uint32_t (&kd)[KD_WORDS], const uint32_t *wsl, uint32_t sb_entry = FDGPU_WS_SB,
-                   const uint32_t *ta = nullptr) {
-  if (!ta) ta = tab_a(wsl);               /* the -A table: own workspace, or the key cache's */
+FDG_DEV void dsm_k(ge_p2 &acc2, uint32_t (&kd)[KD_WORDS], const uint32_t *aux, const uint32_t *ta) {
+  /* ta: the -A table, own workspace or the key cache's */
   ge_p3 acc3;
   ge_p1p1 t;
   uint32_t q[40];
@@ -144,7 +116,7 @@ FDG_DEV void dsm_k(ge_p2 &acc2, uint32_t (&kd)[KD_WORDS], const uint32_t *wsl, u
   /* + [S]B (parked cached form) */
   ge_p1p1_to_p3(acc3, t);
   uint32_t qs[40];
-  atab_load(qs, wsl, (int)sb_entry);
+  sb_load(qs, aux);
   ge_add_cached_regs(t, acc3, qs, false);
   ge_p1p1_to_p2(acc2, t);
 }
@@ -212,8 +184,8 @@ FDG_DEV void atab_build(uint32_t *wsl, const ge_p3 &An) {   /* wsl: the table's 
   ge_p1p1 t; ge_p2 a2; ge_p3 P;
   ge_p3_to_p2(a2, An); ge_dbl(t, a2); ge_p1p1_to_p3(P, t);          /* 2(-A) */
   ge_p3_to_cached(c, P); atab_store(wsl, 2, c);
-  const uint32_t *ent1 = wsl + 1u * FDGPU_ATAB_WORDS;
-  auto ld1 = [ent1](int cc, int w) { return ent1[atab_pos(10 * cc + w)]; };
+  const uint32_t *ent1 = wsl + 1u * FDGPU_PTAB_WORDS;
+  auto ld1 = [ent1](int cc, int w) { return atab_limb(ent1, cc, w); };
 #pragma unroll 1
   for (uint32_t e = 3; e < FDGPU_ATAB_ENTRIES; e++) {
     if (e & 1u) {
@@ -229,8 +201,17 @@ FDG_DEV void atab_build(uint32_t *wsl, const ge_p3 &An) {   /* wsl: the table's 
   }
 }
 
+/* lane i's 16 table entries (2 KiB, line-aligned) */
 FDG_DEV uint32_t *lane_ws(uint32_t *ws, uint32_t i) {
-  return ws + (size_t)i * FDGPU_WS_LANE_WORDS;
+  return ws + (size_t)i * FDGPU_WS_TAB_WORDS;
+}
+/* lane i's aux words (park entry, [w]B), counted back from the aux region's
+   end, which is the fallback queue's first word (fdgpu_ws_layout) */
+FDG_DEV uint32_t *lane_aux(uint32_t *queue, uint32_t i) {
+  return queue - ((size_t)i + 1u) * FDGPU_WS_AUX_WORDS;
+}
+FDG_DEV const uint32_t *lane_aux(const uint32_t *queue, uint32_t i) {
+  return queue - ((size_t)i + 1u) * FDGPU_WS_AUX_WORDS;
 }
 
 /* Output slot of lane i: signatures may be verified in an order grouped by
@@ -254,12 +235,14 @@ FDG_DEV uint32_t out_idx(const uint32_t *__restrict__ perm, uint32_t i) { return
    A lane whose split fails (hs_split_t.ok == false) keeps k's digits and
    [S]B and is finished by fdgpu_full_kernel with the full-length chain. */
 
-/* park words (entry FDGPU_WS_PARK) */
+/* park words (a lane's aux words from FDGPU_AUX_PARK) */
 #define HPARK_KD 0        /* 8 words: radix-16 digits of k (full-path lanes) */
 #define HPARK_CODE 30     /* pass-1 code */
 /* (decoded R is not parked: fdgpu_full_kernel compares with the -R table's
    entry 1, projectively, so a half-size lane never writes this entry) */
-static_assert(HPARK_KD + KD_WORDS <= HPARK_CODE && HPARK_CODE < (int)FDGPU_ATAB_WORDS, "park layout");
+static_assert(HPARK_KD + KD_WORDS <= HPARK_CODE && HPARK_CODE < (int)FDGPU_AUX_SB - (int)FDGPU_AUX_PARK &&
+              FDGPU_AUX_SB + FDGPU_ATAB_WORDS <= FDGPU_WS_AUX_WORDS && FDGPU_AUX_SB % 4u == 0 && FDGPU_WS_AUX_WORDS % 4u == 0,
+              "aux layout");
 
 /* Signed radix-16 digits of a magnitude m < 2^160 (5 limbs): 40 nibbles in
    [-8, 7] (two's complement, digit i at bits 4(i%8) of word i/8); nd = the
@@ -322,48 +305,14 @@ FDG_DEV void hs_wscalar(uint32_t (&w)[8], const uint32_t (&v)[5], bool v_neg, co
   }
 }
 
-/* Table entries of the chain are staged through LDS by LDS-DMA
-   (global_load_lds_dwordx4: no VGPR destination), issued at the start of a
-   window and read back after its doublings, so no 40-word entry stays live
-   in VGPRs across the doublings.  One wave-instruction moves 16 B for each
-   of the 64 lanes into 1 KiB of LDS (wave-uniform base + 16 B x lane).
-   Both entries of a window go through LDS (2 x 10 KiB per wave). */
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-FDG_DEV void stage_entry(uint32_t *lds_wave, const uint32_t *tab, int e) {
-  const uint32_t *src = tab_entry(tab, e);
-  constexpr int NCH = 10;
-#pragma unroll
-  for (int c = 0; c < NCH; c++)
-    __builtin_amdgcn_global_load_lds((const void *)(src + 4 * c), (lds_void_t *)(lds_wave + 256 * c), 16, 0, 0);
-}
-
-/* The staged entry of a signed digit: q[0..9] = Y+X of the digit's point
-   (Y-X of the table's -kP when neg), q[10..19] the other, 2Z, 2dT as stored
-   (2dT still to be negated when neg).  With the pair-interleaved entries the
-   swap is the 8-B offset of two ds_read_b64 per pair chunk. */
-FDG_DEV void unstage_entry_signed(uint32_t (&q)[40], const uint32_t *lds_wave, bool neg) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t *a = lds_wave + 4 * lane + (neg ? 2u : 0u), *b = lds_wave + 4 * lane + (neg ? 0u : 2u);
-#pragma unroll
-  for (int c = 0; c < 5; c++) {
-    const uint2 x = *(const uint2 *)(a + 256 * c), y = *(const uint2 *)(b + 256 * c);
-    q[2 * c] = x.x; q[2 * c + 1] = x.y; q[10 + 2 * c] = y.x; q[10 + 2 * c + 1] = y.y;
-  }
-#pragma unroll
-  for (int c = 5; c < 10; c++) {
-    const uint4 v = *(const uint4 *)(lds_wave + 256 * c + 4 * lane);
-    q[4 * c] = v.x; q[4 * c + 1] = v.y; q[4 * c + 2] = v.z; q[4 * c + 3] = v.w;
-  }
-}
-
 /* [|u|](T_A) + [|v|](T_R), digit strings pre-shifted so that digit nwin-1
    sits in the top nibble; u_neg / v_neg flip every digit's sign (the tables
    hold -A, -R).  Leaves the completed sum of the last addition in t. */
 FDG_DEV void hs_chain(ge_p1p1 &t, uint32_t (&ud)[5], uint32_t (&vd)[5], bool u_neg, bool v_neg, uint32_t nwin,
                       const uint32_t *wsl, const uint32_t *ta) {
   const uint32_t *tr = tab_r(const_cast<uint32_t *>(wsl));
-  __shared__ uint32_t s_stage[FDGPU_BLOCK / 64][2][10 * 256];
+  __shared__ uint32_t s_stage[FDGPU_BLOCK / 64][2][FDGPU_STAGE_WAVE_WORDS];
+  static_assert(sizeof(s_stage) == FDGPU_STAGE_LDS, "FDGPU_SPREAD_LDS is derived from this");
   uint32_t *st_r = &s_stage[threadIdx.x >> 6][0][0];
   uint32_t *st_a = &s_stage[threadIdx.x >> 6][1][0];
   ge_p2 acc2;
@@ -495,7 +444,7 @@ FDG_DEV void verify_hs_body(const uint8_t *__restrict__ arena, const fdgpu_sig_d
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) nb = max(nb, (uint32_t)__shfl_xor((int)nb, off));
   uint32_t *wsl = lane_ws(ws, i);
-  uint32_t *park = wsl + FDGPU_WS_PARK * FDGPU_ATAB_WORDS;
+  uint32_t *aux = lane_aux(queue, i);
   const uint32_t *ta = tab_a(wsl);             /* this lane's -A table */
   FDGPU_STAMP(0);
   uint32_t Renc[8], Aenc[8];
@@ -570,9 +519,9 @@ FDG_DEV void verify_hs_body(const uint8_t *__restrict__ arena, const fdgpu_sig_d
     ge_p3 WB;
     comb_sb(WB, w, btab);
     ge_cached c; ge_p3_to_cached(c, WB);
-    atab_store(wsl, FDGPU_WS_SB, c);
+    sb_store(aux, c);
   }
-  if (full) park_full(park, k);
+  if (full) park_full(aux + FDGPU_AUX_PARK, k);
   FDGPU_STAMP(6);
   bool eq = false;
   if (__any(half)) {
@@ -584,7 +533,7 @@ FDG_DEV void verify_hs_body(const uint8_t *__restrict__ arena, const fdgpu_sig_d
     hs_chain(t, ud, vd, hs.u_neg, hs.v_neg, nwin, wsl, ta);
     /* chain == -[w]B:  x = X/Z = -(YpX - YmX)/Z2,  y = Y/T = (YpX + YmX)/Z2 */
     uint32_t q[40];
-    atab_load(q, wsl, (int)FDGPU_WS_SB);
+    sb_load(q, aux);
     fe ypx, ymx, z2, xw, yw, l1, l2;
 #pragma unroll
     for (int j = 0; j < 10; j++) { ypx.v[j] = q[j]; ymx.v[j] = q[10 + j]; z2.v[j] = q[20 + j]; }
@@ -693,7 +642,8 @@ fdgpu_verify_hs_multi_kernel(const fdgpu_mbatch_t *__restrict__ mb, const uint32
 /* [|d|](+-T) for one table, digits pre-shifted so that digit nwin-1 sits in
    the top nibble; staged through LDS like hs_chain (one entry per window). */
 FDG_DEV void hs_chain1(ge_p1p1 &t, uint32_t (&dd)[5], bool neg, uint32_t nwin, const uint32_t *tab) {
-  __shared__ uint32_t s_stage1[FDGPU_BLOCK / 64][10 * 256];
+  __shared__ uint32_t s_stage1[FDGPU_BLOCK / 64][FDGPU_STAGE_WAVE_WORDS];
+  static_assert(sizeof(s_stage1) == FDGPU_STAGE_LDS_PAIR, "FDGPU_SPREAD_LDS_PAIR is derived from this");
   uint32_t *st = &s_stage1[threadIdx.x >> 6][0];
   ge_p2 acc2;
   ge_p3 acc3;
@@ -742,6 +692,7 @@ fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc
   const fdgpu_sig_desc_t d = sigs[active ? i : n_sig - 1];
   const uint32_t nb = wave_max_u32(sha512_hram_blocks(d.msg_sz));
   uint32_t *wsl = lane_ws(ws, i);             /* i < the workspace's lanes: ceil(n / 128) x 128 <= ceil(n / 256) x 256 */
+  uint32_t *aux = lane_aux(queue, i);
   uint32_t *tab = rl ? tab_r(wsl) : tab_a(wsl);                 /* the lane's own table */
   uint32_t Renc[8], Aenc[8];
   load32(Renc, arena + d.sig_off);
@@ -789,9 +740,9 @@ fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc
     ge_p1p1 tw; ge_add_cached(tw, WB, c, false);
     ge_p1p1_to_p3(WB, tw);
     ge_p3_to_cached(c, WB);
-    if (!rl) atab_store(wsl, FDGPU_WS_SB, c);
+    if (!rl) sb_store(aux, c);
   }
-  if (full && !rl) park_full(wsl + FDGPU_WS_PARK * FDGPU_ATAB_WORDS, k);
+  if (full && !rl) park_full(aux + FDGPU_AUX_PARK, k);
   bool eq = false;
   if (__any(half)) {
     const uint32_t nwin = wave_max_u32(half ? nd_lane : 1u);
@@ -814,7 +765,7 @@ fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc
     ge_add_cached(t, mine, oc, false);
     /* chain == -[w]B (the A lane parked [w]B; a lane reads its own pair's entry) */
     uint32_t q[40];
-    atab_load(q, wsl, (int)FDGPU_WS_SB);
+    sb_load(q, aux);
     fe ypx, ymx, z2, xw, yw, l1, l2;
 #pragma unroll
     for (int j = 0; j < 10; j++) { ypx.v[j] = q[j]; ymx.v[j] = q[10 + j]; z2.v[j] = q[20 + j]; }
@@ -942,13 +893,13 @@ FDG_DEV void full_body(uint32_t *__restrict__ ws, const uint32_t *__restrict__ p
   if (bx * blockDim.x >= cnt) return;
   for (uint32_t q = bx * blockDim.x + threadIdx.x; q < cnt; q += slots) {
     const uint32_t i = queue[q];
-    uint32_t *wsl = ws + (size_t)i * FDGPU_WS_LANE_WORDS;
-    const uint32_t *park = wsl + FDGPU_WS_PARK * FDGPU_ATAB_WORDS;
+    uint32_t *wsl = lane_ws(ws, i);
+    const uint32_t *aux = lane_aux(queue, i), *park = aux + FDGPU_AUX_PARK;
     uint32_t kd[KD_WORDS];
 #pragma unroll
     for (int j = 0; j < KD_WORDS; j++) kd[j] = park[HPARK_KD + j];
     ge_p2 Rc;
-    dsm_k(Rc, kd, wsl, FDGPU_WS_SB, tab_a(key_of ? lane_ws(ws, key_of[i]) : wsl));
+    dsm_k(Rc, kd, aux, tab_a(key_of ? lane_ws(ws, key_of[i]) : wsl));
     /* == R: the -R table's entry 1 is (Y-X, Y+X, 2Z, -2dT) of R = (X:Y:Z),
        so 2X = YmX - YpX and 2Y = YpX + YmX; compare X / Z, Y / Z crosswise */
     uint32_t er[40];

@@ -489,6 +489,15 @@ class VerifyEngine:
         self._chk(_lib.lib().fdgpu_debug_sc_recode(self._h, s.ctypes.data, len(s), out.ctypes.data), "debug_sc_recode")
         return out
 
+    def debug_tabpack(self, ent):
+        """ent: uint32[n, 40] raw limbs of cached entries (Y+X, Y-X, 2Z, 2dT)
+        -> (uint32[n, 32] the stored packed words, uint32[n, 3, 40] the limbs
+        read back by atab_load, by the LDS path, and by the LDS path with neg)"""
+        ent = np.ascontiguousarray(ent, dtype=np.uint32).reshape(-1, 40)
+        out = np.zeros((len(ent), 160), dtype=np.uint32)
+        self._chk(_lib.lib().fdgpu_debug_tabpack(self._h, ent.ctypes.data, len(ent), out.ctypes.data), "debug_tabpack")
+        return out[:, :32].copy(), out[:, 32:152].reshape(-1, 3, 40).copy()
+
     def debug_btab(self):
         """The engine's fixed-base comb table -> uint32[NDIG, entries, stride]"""
         d = bcomb_dims()

@@ -42,11 +42,16 @@ OUT_DEPTH = 1 << 14
 DEDUP_TCACHE_DEPTH = 4194302
 
 
-def _wait_file(path, procs, timeout):
+def _wait_file(path, procs, timeout, owner=None):
+    """Wait for `path`, the ready file of `owner` (one of procs).  A process
+    that ends before the file exists is an error, except another engine
+    process that ended cleanly: over prefilled links an engine whose own
+    ready file is long written can finish its whole share (tens of ms) while
+    a sibling is still opening its device."""
     t0 = time.monotonic()
     while not os.path.exists(path):
         for p in procs:
-            if p.poll() is not None:
+            if p.poll() is not None and (p.returncode != 0 or owner is None or p is owner):
                 out, err = p.communicate()
                 raise RuntimeError(f"{p.args[:3]} exited ({p.returncode}) before {os.path.basename(path)}: "
                                    f"{err[-3000:] if err else ''}")
@@ -140,8 +145,8 @@ def run(npz, n_payloads, tiles=1, producers=1, mode="paced", rate=0.0, reps=1, d
             feed = _finish(subprocess.Popen(feed_cmd, **popen), timeout, "quic_feed")
         engs = [subprocess.Popen(c, **popen) for c in eng_cmds]
         procs += engs
-        for r in readies:
-            _wait_file(r, engs, timeout)
+        for r, eng in zip(readies, engs):
+            _wait_file(r, engs, timeout, owner=eng)
         dd = None
         if dedup:
             dd_cmd = [sys.executable, "-m", "firedancer_amd.dedup_proc", *sum([["--in", p] for p in vd], []),
