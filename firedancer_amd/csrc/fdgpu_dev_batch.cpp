@@ -107,13 +107,11 @@ fdgpu_dev_batch_t *fdgpu_dev_batch_upload(fdgpu_engine_t *e, uint8_t const *aren
   fdgpu_dev_batch *b = new fdgpu_dev_batch();
   b->n_sig = (uint64_t)ns; b->n_txn = txn_cnt;
   auto fail = [&](const char *what) -> fdgpu_dev_batch_t * { set_err("%s", what); fdgpu_dev_batch_free(e, b); return nullptr; };
-  if (b->d_arena.alloc(arena_sz + FDGPU_ARENA_SLACK) != hipSuccess) return fail("arena alloc");
+  if (dev_arena(b->d_arena, arena, arena_sz) != hipSuccess) return fail("arena upload");
   if (b->d_sigs.alloc((ns + 1) * sizeof(fdgpu_sig_desc_t)) != hipSuccess) return fail("sig alloc");
   if (b->d_txns.alloc((txn_cnt + 1) * sizeof(fdgpu_txn_desc_t)) != hipSuccess) return fail("txn alloc");
   if (b->d_sig_codes.alloc(ns + 16) != hipSuccess) return fail("code alloc");
   if (b->d_txn_codes.alloc(txn_cnt + 16) != hipSuccess) return fail("code alloc");
-  if (hipMemset(b->d_arena, 0, arena_sz + FDGPU_ARENA_SLACK) != hipSuccess) return fail("memset");
-  if (arena_sz && hipMemcpy(b->d_arena, arena, arena_sz, hipMemcpyHostToDevice) != hipSuccess) return fail("h2d");
   if (ns && hipMemcpy(b->d_sigs, sd.data(), ns * sizeof(fdgpu_sig_desc_t), hipMemcpyHostToDevice) != hipSuccess) return fail("h2d");
   if (ns && !pm.empty()) {
     if (b->d_perm.alloc(ns * sizeof(uint32_t)) != hipSuccess) return fail("perm alloc");
@@ -149,16 +147,14 @@ fdgpu_dev_batch_t *fdgpu_dev_batch_upload_frags(fdgpu_engine_t *e, uint8_t const
   b->n_sig_bound = bound;
   auto fail = [&](const char *what) -> fdgpu_dev_batch_t * { set_err("%s", what); fdgpu_dev_batch_free(e, b); return nullptr; };
   const uint64_t nt = frag_cnt + 1;
-  if (b->d_arena.alloc(arena_sz + FDGPU_ARENA_SLACK) != hipSuccess) return fail("arena alloc");
+  if (dev_arena(b->d_arena, arena, arena_sz) != hipSuccess) return fail("arena upload");
   if (b->d_frags.alloc(nt * sizeof(fdgpu_frag_t)) != hipSuccess) return fail("frag alloc");
   if (const char *what = b->pb.alloc(frag_cnt)) return fail(what);
   if (b->d_sigs.alloc((bound + 1) * sizeof(fdgpu_sig_desc_t)) != hipSuccess) return fail("sig alloc");
   if (b->d_txns.alloc(nt * sizeof(fdgpu_txn_desc_t)) != hipSuccess) return fail("txn alloc");
   if (b->d_sig_codes.alloc(bound + 16) != hipSuccess) return fail("code alloc");
   if (b->d_txn_codes.alloc(frag_cnt + 16) != hipSuccess) return fail("code alloc");
-  if (hipMemset(b->d_arena, 0, arena_sz + FDGPU_ARENA_SLACK) != hipSuccess) return fail("memset");
   if (hipMemset(b->pb.n_sig, 0, sizeof(uint32_t)) != hipSuccess) return fail("memset");
-  if (arena_sz && hipMemcpy(b->d_arena, arena, arena_sz, hipMemcpyHostToDevice) != hipSuccess) return fail("h2d");
   if (frag_cnt && hipMemcpy(b->d_frags, frags, frag_cnt * sizeof(fdgpu_frag_t), hipMemcpyHostToDevice) != hipSuccess)
     return fail("h2d");
   if (bound > e->ws_sig) {
@@ -223,8 +219,8 @@ int fdgpu_dev_batch_time2(fdgpu_engine_t *e, fdgpu_dev_batch_t *b, int iters, do
     const int wrc = ensure_ws(e, nsig);
     if (wrc) return wrc;
   }
-  std::vector<hipEvent_t> ev(4 * (size_t)iters + 1);
-  for (auto &x : ev) HIPCHK(hipEventCreate(&x), FDGPU_ERR_DEVICE);
+  Events ev;
+  if (!ev.create(4 * (size_t)iters + 1)) { (void)hipGetLastError(); set_err("event"); return FDGPU_ERR_DEVICE; }
   int rc = FDGPU_OK;
   for (int i = 0; i < iters && rc == FDGPU_OK; i++) {
     if (hipEventRecord(ev[4 * i], st) != hipSuccess) rc = FDGPU_ERR_DEVICE;
@@ -258,7 +254,6 @@ int fdgpu_dev_batch_time2(fdgpu_engine_t *e, fdgpu_dev_batch_t *b, int iters, do
   } else {
     set_err("timing launch failed");
   }
-  for (auto &x : ev) (void)hipEventDestroy(x);
   return rc;
 }
 

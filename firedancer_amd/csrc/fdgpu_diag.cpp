@@ -1,6 +1,8 @@
 /* fdgpu_diag.cpp -- the fdgpu_debug_* diagnostics that run the kernels' building blocks (field, decode, SHA-512,
-   scalar) on caller data, for the parity tests.  Synchronous, on the engine's compute stream. */
+   SHA-256, scalar) on caller data, for the parity tests, and the two-stage timer of the fdgpu_debug_*_time ones.
+   Synchronous, on the engine's compute stream. */
 #include "fdgpu_engine.h"
+#include "fdgpu_shred.h"
 
 using namespace fdgpu;
 
@@ -8,14 +10,17 @@ using namespace fdgpu;
 #define DALLOC(buf, n) do { if ((buf).alloc((size_t)(n) * sizeof(*(buf).p) + 64) != hipSuccess) { \
   set_err("alloc"); return FDGPU_ERR_DEVICE; } } while (0)
 
+/* n messages of the arena (with their signature and key, sig_pub) through one of the hash test kernels, out_bytes each
+   back */
+using MsgLaunch = hipError_t (*)(const uint8_t *, const fdgpu_sig_desc_t *, uint32_t, uint32_t *, hipStream_t);
 static int debug_msgs(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *txns, uint64_t n,
-                      uint8_t *out, int hram) {
+                      uint8_t *out, MsgLaunch launch, uint64_t out_bytes, bool sig_pub) {
   if (!e || !n) return FDGPU_ERR_INVAL;
   HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
   std::vector<fdgpu_sig_desc_t> d(n);
   for (uint64_t i = 0; i < n; i++) {
     if ((uint64_t)txns[i].msg_off + txns[i].msg_sz > arena_sz ||
-        (hram && ((uint64_t)txns[i].sig_off + 64 > arena_sz || (uint64_t)txns[i].pub_off + 32 > arena_sz))) {
+        (sig_pub && ((uint64_t)txns[i].sig_off + 64 > arena_sz || (uint64_t)txns[i].pub_off + 32 > arena_sz))) {
       set_err("descriptor out of bounds"); return FDGPU_ERR_INVAL;
     }
     d[i].msg_off = txns[i].msg_off; d[i].msg_sz = txns[i].msg_sz;
@@ -23,19 +28,14 @@ static int debug_msgs(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz
   }
   DevBuf<uint8_t> da;
   DevBuf<fdgpu_sig_desc_t> dd;
-  DevBuf<uint32_t> dout;
-  DALLOC(da, arena_sz + FDGPU_ARENA_SLACK);
+  DevBuf<uint8_t> dout;
+  HIPCHK(dev_arena(da, arena, arena_sz), FDGPU_ERR_DEVICE);
   DALLOC(dd, n);
-  DALLOC(dout, n * 16);
-  HIPCHK(hipMemset(da, 0, arena_sz + FDGPU_ARENA_SLACK), FDGPU_ERR_DEVICE);
-  if (arena_sz) HIPCHK(hipMemcpy(da, arena, arena_sz, hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
+  DALLOC(dout, n * out_bytes);
   HIPCHK(hipMemcpy(dd, d.data(), n * sizeof(fdgpu_sig_desc_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
-  if (hram)
-    HIPCHK(fdgpu_launch_test_hram(da, dd, (uint32_t)n, dout, e->compute), FDGPU_ERR_DEVICE);
-  else
-    HIPCHK(fdgpu_launch_test_sha512(da, dd, (uint32_t)n, dout, e->compute), FDGPU_ERR_DEVICE);
+  HIPCHK(launch(da, dd, (uint32_t)n, (uint32_t *)dout.p, e->compute), FDGPU_ERR_DEVICE);
   HIPCHK(hipStreamSynchronize(e->compute), FDGPU_ERR_DEVICE);
-  HIPCHK(hipMemcpy(out, dout, n * (hram ? 32 : 64), hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(out, dout, n * out_bytes, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
   return FDGPU_OK;
 }
 
@@ -55,6 +55,27 @@ static int debug_map(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint64_t 
   return FDGPU_OK;
 }
 
+/* The device time of two stages of a pipeline on st, for fdgpu_debug_<what>_time: one warm-up (it runs both stages,
+   and leaves what the second reads of the first), then iters runs of the first between two events and iters of the
+   second between the next two; the means in ms.  Every callable answers whether its launches were queued. */
+int fdgpu::time_two_stages(hipStream_t st, int iters, const char *what, const std::function<bool()> &warm,
+                           const std::function<bool()> &first, const std::function<bool()> &second, double *first_ms,
+                           double *second_ms) {
+  Events ev;
+  if (!ev.create(3)) { (void)hipGetLastError(); set_err("event"); return FDGPU_ERR_DEVICE; }
+  bool ok = warm() && hipEventRecord(ev[0], st) == hipSuccess;
+  for (int i = 0; i < iters && ok; i++) ok = first();
+  ok = ok && hipEventRecord(ev[1], st) == hipSuccess;
+  for (int i = 0; i < iters && ok; i++) ok = second();
+  ok = ok && hipEventRecord(ev[2], st) == hipSuccess && hipEventSynchronize(ev[2]) == hipSuccess;
+  float a = 0.f, b = 0.f;
+  ok = ok && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess;
+  if (!ok) { (void)hipGetLastError(); set_err("%s timing failed", what); return FDGPU_ERR_DEVICE; }
+  *first_ms = a / iters;
+  *second_ms = b / iters;
+  return FDGPU_OK;
+}
+
 extern "C" {
 
 int fdgpu_debug_fe_ops(fdgpu_engine_t *e, uint8_t const *ab, uint64_t n, uint8_t *out) {
@@ -70,12 +91,18 @@ int fdgpu_debug_decode(fdgpu_engine_t *e, uint8_t const *enc, uint64_t n, int re
 
 int fdgpu_debug_sha512(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *msgs,
                        uint64_t n, uint8_t *out) {
-  return debug_msgs(e, arena, arena_sz, msgs, n, out, 0);
+  return debug_msgs(e, arena, arena_sz, msgs, n, out, fdgpu_launch_test_sha512, 64, false);
 }
 
 int fdgpu_debug_hram(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *txns,
                      uint64_t n, uint8_t *out) {
-  return debug_msgs(e, arena, arena_sz, txns, n, out, 1);
+  return debug_msgs(e, arena, arena_sz, txns, n, out, fdgpu_launch_test_hram, 32, true);
+}
+
+int fdgpu_debug_sha256(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *msgs, uint64_t n,
+                       uint8_t *out) {
+  if (!e || !n || !msgs || !out || (!arena && arena_sz) || arena_sz > 0xFFFFFF00ull) { set_err("bad argument"); return FDGPU_ERR_INVAL; }
+  return debug_msgs(e, arena, arena_sz, msgs, n, out, fdgpu_launch_test_sha256, 32, false);
 }
 
 int fdgpu_debug_sc_reduce(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint8_t *out) {
@@ -143,12 +170,10 @@ int fdgpu_debug_sig_codes(fdgpu_engine_t *e, uint8_t const *arena, uint64_t aren
   DevBuf<fdgpu_sig_desc_t> dd;
   DevBuf<uint32_t> dp;
   DevBuf<int8_t> dc;
-  DALLOC(da, arena_sz + FDGPU_ARENA_SLACK);
+  HIPCHK(dev_arena(da, arena, arena_sz), FDGPU_ERR_DEVICE);
   DALLOC(dd, ns);
   DALLOC(dp, ns);
   DALLOC(dc, ns);
-  HIPCHK(hipMemset(da, 0, arena_sz + FDGPU_ARENA_SLACK), FDGPU_ERR_DEVICE);
-  HIPCHK(hipMemcpy(da, arena, arena_sz, hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
   HIPCHK(hipMemcpy(dd, sd.data(), ns * sizeof(fdgpu_sig_desc_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
   if (perm) HIPCHK(hipMemcpy(dp, perm, ns * sizeof(uint32_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
   const uint32_t flags = kflags(e);

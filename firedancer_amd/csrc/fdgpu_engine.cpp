@@ -203,6 +203,15 @@ bool slot_io_bufs(Slot &s, const fdgpu_cfg_t &c) {
   return true;
 }
 
+/* The slot's item_results() of max_txn + 1 items and their pinned read-back, on its first shred or PoH batch.  d_res,
+   whose presence says both are there, is allocated last: a failure part-way is retried by the next batch. */
+bool slot_res_bufs(Slot &s, const fdgpu_cfg_t &c) {
+  if (s.d_res) return true;
+  HIPCHK(s.h_res.alloc(item_results(c.max_txn + 1).bytes), false);
+  HIPCHK(s.d_res.alloc(item_results(c.max_txn + 1).bytes), false);
+  return true;
+}
+
 /* (Re)size the per-lane workspace to cover n_sig signatures. */
 int ensure_ws(fdgpu_engine *e, uint64_t n_sig) {
   if (n_sig <= e->ws_sig && e->d_ws) return FDGPU_OK;

@@ -99,6 +99,38 @@ template <class T, bool Host> struct HipBuf {
 template <class T> using DevBuf = HipBuf<T, false>;
 template <class T> using HostBuf = HipBuf<T, true>;
 
+/* A batch's arena resident on the device for the synchronous paths (the diagnostics, fdgpu_dev_batch_upload*): arena_sz
+   + extra + FDGPU_ARENA_SLACK bytes, zeroed -- all of them, or only those past the arena -- with the arena copied in. */
+inline hipError_t dev_arena(DevBuf<uint8_t> &d, uint8_t const *arena, uint64_t arena_sz, uint64_t extra = 0,
+                            bool zero_all = true) {
+  const uint64_t bytes = arena_sz + extra + FDGPU_ARENA_SLACK, z0 = zero_all ? 0 : arena_sz;
+  hipError_t rc = d.alloc(bytes);
+  if (rc == hipSuccess) rc = hipMemset(d.p + z0, 0, bytes - z0);
+  if (rc == hipSuccess && arena_sz) rc = hipMemcpy(d, arena, arena_sz, hipMemcpyHostToDevice);
+  return rc;
+}
+
+/* N timing events: create makes all of them or none (what it made before a failure is destroyed), and they go with
+   their owner. */
+struct Events {
+  std::vector<hipEvent_t> ev;
+  Events() = default;
+  Events(const Events &) = delete;
+  Events &operator=(const Events &) = delete;
+  ~Events() { clear(); }
+  void clear() { for (hipEvent_t x : ev) (void)hipEventDestroy(x); ev.clear(); }
+  bool create(size_t n) {
+    clear();
+    while (ev.size() < n) {
+      hipEvent_t x;
+      if (hipEventCreate(&x) != hipSuccess) { clear(); return false; }
+      ev.push_back(x);
+    }
+    return true;
+  }
+  hipEvent_t operator[](size_t i) const { return ev[i]; }
+};
+
 /* The device-side parse buffers of a frag batch of up to n_txn payloads (fdgpu_launch_frag_ingest and its kin): n_txn
    + 1 entries each, and the scan's block totals.  alloc returns null, or what could not be allocated. */
 struct ParseBufs {
@@ -125,6 +157,14 @@ inline IoResults io_results(uint64_t n) {
   return {cb, cb + n * 8, cb + n * 10};
 }
 
+/* An item batch's results for n items (a shred's root, a PoH entry's hash), in the slot's d_res and its pinned
+   read-back h_res: [codes, padded to 64][32 B per item]. */
+struct ItemResults { uint64_t items, bytes; };
+inline ItemResults item_results(uint64_t n) {
+  const uint64_t cb = (n + 63) & ~63ull;
+  return {cb, cb + n * 32};
+}
+
 /* A gathered batch's pinned record area for n frags (h_io, read in place by the ingest kernel), each part 64-B
    aligned: the frag records at 0, the payloads' device-side addresses, the re-check pairs {mcache line address, seq},
    the DMA gather's range table.  bytes keeps the 192 B of slack the earlier size formula had, so no allocation
@@ -141,8 +181,8 @@ enum class Batch : uint8_t {
   Ring,     /* fdgpu_submit / fdgpu_stage_submit: codes in h_codes */
   Frag,     /* fdgpu_submit_frags: [codes][trailers] in h_tr */
   FragIo,   /* fdgpu_submit_frags_io: io_results() in h_tr */
-  Shred,    /* fdgpu_submit_shreds: [codes, padded to 64][roots] in h_shres */
-  Poh,      /* fdgpu_submit_poh: [codes, padded to 64][hashes] in h_pres */
+  Shred,    /* fdgpu_submit_shreds: item_results() in h_res, the items the roots */
+  Poh,      /* fdgpu_submit_poh: item_results() in h_res, the items the hashes */
 };
 
 struct Slot {
@@ -191,18 +231,18 @@ struct Slot {
                                                  engines, parsed and verified in place (the batch arena) */
   uint64_t mirror_cap = 0;
   uint8_t *d_trh = nullptr;                   /* h_tr's device-side address (results written in place) */
-  /* shred batches (fdgpu_submit_shreds), allocated on the slot's first one for max_txn shreds: the records, the
-     ingest's signature count, and the results [codes, padded to 64][32-B roots] with their pinned read-back */
+  /* shred and PoH batches: item_results() of max_txn + 1 items and their pinned read-back, allocated on the slot's
+     first batch of either kind (slot_res_bufs) */
+  DevBuf<uint8_t> d_res; HostBuf<uint8_t> h_res;
+  /* shred batches (fdgpu_submit_shreds), allocated on the slot's first one for max_txn shreds: the records and the
+     ingest's signature count */
   HostBuf<fdgpu_shred_t> h_sh; DevBuf<fdgpu_shred_t> d_sh;
   DevBuf<uint32_t> d_sh_cnt;
-  DevBuf<uint8_t> d_shres; HostBuf<uint8_t> h_shres;
   /* PoH batches (fdgpu_submit_poh), allocated on the slot's first one for max_txn entries and max_sig signatures:
-     the entries, the signatures' arena offsets, the queue (entry indices, longest chain first) and its head, the
-     tree's nodes (32 B per signature), and the results [codes, padded to 64][32-B hashes] with their pinned
-     read-back */
+     the entries, the signatures' arena offsets, the queue (entry indices, longest chain first) and its head, and the
+     tree's nodes (32 B per signature) */
   HostBuf<fdgpu_poh_entry_t> h_pe; DevBuf<fdgpu_poh_entry_t> d_pe;
   HostBuf<uint32_t> h_psig, h_pord; DevBuf<uint32_t> d_psig, d_pord, d_pnodes, d_phead;
-  DevBuf<uint8_t> d_pres; HostBuf<uint8_t> h_pres;
   /* FDGPU_FLAG_MERGE: the batch's gather + parse are queued and its verify waits to be merged with the other batches
      ready (merge_kick), which then queues the rest of the batch behind it */
   hipEvent_t parsed = nullptr;
@@ -282,6 +322,7 @@ uint32_t ring_kflags(fdgpu_engine_t *e, Slot *s, uint64_t n_sig);  /* ... of slo
 bool slot_ws(Slot &s, uint64_t n_sig);
 bool slot_frag_bufs(Slot &s, const fdgpu_cfg_t &c, uint64_t tr);
 bool slot_io_bufs(Slot &s, const fdgpu_cfg_t &c);
+bool slot_res_bufs(Slot &s, const fdgpu_cfg_t &c);
 const fdgpu_engine::Reg *region_of(const fdgpu_engine *e, uintptr_t p, uint64_t sz);
 int ensure_ws(fdgpu_engine *e, uint64_t n_sig);
 int enqueue_verify(fdgpu_engine_t *e, const uint8_t *d_arena, const fdgpu_sig_desc_t *d_sigs, const uint32_t *d_perm,
@@ -289,8 +330,8 @@ int enqueue_verify(fdgpu_engine_t *e, const uint8_t *d_arena, const fdgpu_sig_de
                    int8_t *d_txn_codes, hipStream_t st, uint32_t *ws = nullptr, uint32_t flags = ~0u);
 
 /* fdgpu_ring.cpp */
-Slot *free_slot(fdgpu_engine_t *e);
-uint64_t stage_arena(fdgpu_engine_t *e, Slot *s, uint8_t const *arena, uint64_t sz);
+int take_slot(fdgpu_engine_t *e, Slot **s);
+int slot_upload(fdgpu_engine_t *e, Slot *s, uint8_t const *arena, uint64_t arena_sz);
 int slot_signal(fdgpu_engine_t *e, Slot *s);
 int64_t slot_publish(fdgpu_engine_t *e, Slot *s, Batch kind, uint64_t txn_cnt, uint64_t tr_sz, uint64_t tr_base,
                      bool signal_deferred = false);
@@ -301,6 +342,11 @@ int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking
 /* fdgpu_frags.cpp */
 int merge_kick(fdgpu_engine_t *e, bool force);
 void submit_prof_report();                     /* Env::submit_prof: the totals so far, to stderr */
+
+/* fdgpu_diag.cpp */
+int time_two_stages(hipStream_t st, int iters, const char *what, const std::function<bool()> &warm,
+                    const std::function<bool()> &first, const std::function<bool()> &second, double *first_ms,
+                    double *second_ms);
 
 /* fdgpu_expand.cpp */
 int64_t expand(uint64_t arena_sz, const fdgpu_txn_t *txns, uint64_t txn_cnt, uint64_t max_sig, fdgpu_sig_desc_t *sigs,

@@ -144,21 +144,10 @@ int64_t fdgpu_submit_frags(fdgpu_engine_t *e, uint8_t const *arena, uint64_t are
   }
   if (bound > e->cfg.max_sig) { set_err("batch may exceed max_sig (%llu)", (unsigned long long)e->cfg.max_sig); return FDGPU_ERR_INVAL; }
   std::lock_guard<std::mutex> lk(e->ring_mu);
-  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
-  Slot *s = free_slot(e);
-  if (!s) { set_err("all ring slots hold unpolled batches"); return FDGPU_ERR_FULL; }
+  Slot *s = nullptr;
+  if (const int rc = take_slot(e, &s)) return rc;
   if (!slot_frag_bufs(*s, e->cfg, trailer_sz) || !slot_ws(*s, bound)) return FDGPU_ERR_DEVICE;
-  /* the slack past the arena needs no zeroing here: every device reader of a frag batch masks the bytes past its
-     payload (fdt_reader, msg_block), only their presence (FDGPU_ARENA_SLACK allocated) matters */
-  if (region_of(e, (uintptr_t)arena, arena_sz)) {
-    if (arena_sz) HIPCHK(hipMemcpyAsync(s->d_arena, arena, arena_sz, hipMemcpyHostToDevice, s->stream), FDGPU_ERR_DEVICE);
-  } else {
-    const uint64_t up = stage_arena(e, s, arena, arena_sz);
-    if (up == UINT64_MAX) return FDGPU_ERR_DEVICE;
-    if (arena_sz > up)
-      HIPCHK(hipMemcpyAsync(s->d_arena + up, s->h_arena + up, arena_sz - up, hipMemcpyHostToDevice, s->stream),
-             FDGPU_ERR_DEVICE);
-  }
+  if (const int rc = slot_upload(e, s, arena, arena_sz)) return rc;
   const uint64_t tr_base = (n + 63) & ~63ull;
   if (n) {
     ParseBufs &pb = s->pb;
@@ -212,9 +201,8 @@ int64_t fdgpu_submit_frags_io(fdgpu_engine_t *e, fdgpu_frag_io_t const *fio, uin
     ldev[l] = rm->dbase + (links[l].mcache - rm->base);
     lmask[l] = d - 1;
   }
-  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
-  Slot *s = free_slot(e);
-  if (!s) { set_err("all ring slots hold unpolled batches"); return FDGPU_ERR_FULL; }
+  Slot *s = nullptr;
+  if (const int rc = take_slot(e, &s)) return rc;
   const IoResults res = io_results(n);         /* in the trailer buffer */
   if (!slot_frag_bufs(*s, e->cfg, res.bytes)) return FDGPU_ERR_DEVICE;
   if (!slot_io_bufs(*s, e->cfg)) return FDGPU_ERR_DEVICE;

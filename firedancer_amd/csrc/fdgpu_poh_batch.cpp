@@ -11,10 +11,6 @@ using namespace fdgpu;
 
 namespace {
 
-/* the results of n entries: [codes, padded to 64][32-B hashes] */
-inline uint64_t res_hashes(uint64_t n) { return (n + 63) & ~63ull; }
-inline uint64_t res_bytes(uint64_t n) { return res_hashes(n) + 32 * n; }
-
 /* Checks every argument of a PoH batch against the entry rules (fdt_poh.h) and the limits given; 0, or
    FDGPU_ERR_INVAL with the error text set. */
 int poh_args(const fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_poh_entry_t const *en, uint64_t n,
@@ -45,12 +41,10 @@ bool slot_poh_bufs(Slot &s, const fdgpu_cfg_t &c) {
   HIPCHK(s.h_pe.alloc(n * sizeof(fdgpu_poh_entry_t)), false);
   HIPCHK(s.h_pord.alloc(n * sizeof(uint32_t)), false);
   HIPCHK(s.h_psig.alloc(ns * sizeof(uint32_t)), false);
-  HIPCHK(s.h_pres.alloc(res_bytes(n)), false);
   HIPCHK(s.d_pord.alloc(n * sizeof(uint32_t)), false);
   HIPCHK(s.d_psig.alloc(ns * sizeof(uint32_t)), false);
   HIPCHK(s.d_pnodes.alloc(ns * 32), false);
   HIPCHK(s.d_phead.alloc(64), false);
-  HIPCHK(s.d_pres.alloc(res_bytes(n)), false);
   HIPCHK(s.d_pe.alloc(n * sizeof(fdgpu_poh_entry_t)), false);
   return true;
 }
@@ -67,7 +61,8 @@ struct DevPoh {
     const int rc = poh_args(e, a, arena_sz, entries, n, so, sig_total, cap, UINT32_MAX - 64ull * 1024);
     if (rc) return rc;
     HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
-    if (arena.alloc(arena_sz + FDGPU_ARENA_SLACK) || res.alloc(res_bytes(n)) || en.alloc(n * sizeof(fdgpu_poh_entry_t)) ||
+    HIPCHK(dev_arena(arena, a, arena_sz, 0, false), FDGPU_ERR_DEVICE);
+    if (res.alloc(item_results(n).bytes) || en.alloc(n * sizeof(fdgpu_poh_entry_t)) ||
         sig_offs.alloc((sig_total + 1) * sizeof(uint32_t)) || order.alloc(n * sizeof(uint32_t)) ||
         nodes.alloc((sig_total + 1) * 32) || head.alloc(64)) {
       (void)hipGetLastError();
@@ -76,8 +71,6 @@ struct DevPoh {
     }
     std::vector<uint32_t> ord(n);
     n_q = poh_order(entries, n, cap, ord.data());
-    HIPCHK(hipMemset(arena.p + arena_sz, 0, FDGPU_ARENA_SLACK), FDGPU_ERR_DEVICE);
-    if (arena_sz) HIPCHK(hipMemcpy(arena, a, arena_sz, hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
     HIPCHK(hipMemcpy(en, entries, n * sizeof(fdgpu_poh_entry_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
     if (sig_total) HIPCHK(hipMemcpy(sig_offs, so, sig_total * sizeof(uint32_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
     if (n_q) HIPCHK(hipMemcpy(order, ord.data(), n_q * sizeof(uint32_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
@@ -88,7 +81,7 @@ struct DevPoh {
   }
   bool chains(uint64_t n, uint64_t cap, uint32_t grid_waves, hipStream_t st) {
     return fdgpu_launch_poh_chains(arena, en, (uint32_t)n, order, n_q, nodes, (uint32_t)cap, grid_waves, head,
-                                   (int8_t *)res.p, res + res_hashes(n), st) == hipSuccess;
+                                   (int8_t *)res.p, res + item_results(n).items, st) == hipSuccess;
   }
 };
 
@@ -101,22 +94,12 @@ int64_t fdgpu_submit_poh(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena
   const int arc = poh_args(e, arena, arena_sz, entries, n, sig_offs, sig_total, hash_cnt_cap, e ? e->cfg.max_arena : 0);
   if (arc) return arc;
   std::lock_guard<std::mutex> lk(e->ring_mu);
-  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
-  Slot *s = free_slot(e);
-  if (!s) { set_err("all ring slots hold unpolled batches"); return FDGPU_ERR_FULL; }
+  Slot *s = nullptr;
+  if (const int rc = take_slot(e, &s)) return rc;
   if (!n) return slot_publish(e, s, Batch::Poh, 0, 0, 0);
-  if (!slot_poh_bufs(*s, e->cfg)) return FDGPU_ERR_DEVICE;
-  /* the slack past the arena needs no zeroing: the loads that run past a signature or a hash are cut to their words
-     in registers (fdgpu_sha256.h), only the bytes' presence matters */
-  if (region_of(e, (uintptr_t)arena, arena_sz)) {
-    if (arena_sz) HIPCHK(hipMemcpyAsync(s->d_arena, arena, arena_sz, hipMemcpyHostToDevice, s->stream), FDGPU_ERR_DEVICE);
-  } else {
-    const uint64_t up = stage_arena(e, s, arena, arena_sz);
-    if (up == UINT64_MAX) return FDGPU_ERR_DEVICE;
-    if (arena_sz > up)
-      HIPCHK(hipMemcpyAsync(s->d_arena + up, s->h_arena + up, arena_sz - up, hipMemcpyHostToDevice, s->stream),
-             FDGPU_ERR_DEVICE);
-  }
+  if (!slot_poh_bufs(*s, e->cfg) || !slot_res_bufs(*s, e->cfg)) return FDGPU_ERR_DEVICE;
+  if (const int rc = slot_upload(e, s, arena, arena_sz)) return rc;
+  const ItemResults res = item_results(n);
   memcpy(s->h_pe, entries, n * sizeof(fdgpu_poh_entry_t));
   if (sig_total) memcpy(s->h_psig, sig_offs, sig_total * sizeof(uint32_t));
   const uint32_t n_q = poh_order(s->h_pe, n, hash_cnt_cap, s->h_pord);
@@ -129,10 +112,10 @@ int64_t fdgpu_submit_poh(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena
   HIPCHK(fdgpu_launch_poh_tree(s->d_arena, s->d_pe, (uint32_t)n, s->d_psig, (uint32_t)sig_total, s->d_pnodes, s->stream),
          FDGPU_ERR_DEVICE);
   HIPCHK(fdgpu_launch_poh_chains(s->d_arena, s->d_pe, (uint32_t)n, s->d_pord, n_q, s->d_pnodes, (uint32_t)hash_cnt_cap, 0,
-                                 s->d_phead, (int8_t *)s->d_pres.p, s->d_pres + res_hashes(n), s->stream),
+                                 s->d_phead, (int8_t *)s->d_res.p, s->d_res + res.items, s->stream),
          FDGPU_ERR_DEVICE);
-  HIPCHK(hipMemcpyAsync(s->h_pres, s->d_pres, res_bytes(n), hipMemcpyDeviceToHost, s->stream), FDGPU_ERR_DEVICE);
-  return slot_publish(e, s, Batch::Poh, n, 32 * n, res_hashes(n));
+  HIPCHK(hipMemcpyAsync(s->h_res, s->d_res, res.bytes, hipMemcpyDeviceToHost, s->stream), FDGPU_ERR_DEVICE);
+  return slot_publish(e, s, Batch::Poh, n, 0, 0);
 }
 
 int fdgpu_poll_poh(fdgpu_engine_t *e, int64_t ticket, int8_t *codes, uint8_t *hashes, int blocking) {
@@ -161,7 +144,7 @@ int fdgpu_debug_poh(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, 
   }
   HIPCHK(hipStreamSynchronize(e->compute), FDGPU_ERR_DEVICE);
   HIPCHK(hipMemcpy(codes, b.res, n, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
-  HIPCHK(hipMemcpy(hashes, b.res + res_hashes(n), 32 * n, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(hashes, b.res + item_results(n).items, 32 * n, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
   return FDGPU_OK;
 }
 
@@ -173,24 +156,11 @@ int fdgpu_debug_poh_time(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena
   const int rc = b.upload(e, arena, arena_sz, entries, n, sig_offs, sig_total, hash_cnt_cap);
   if (rc) return rc;
   hipStream_t st = e->compute;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  for (auto &x : ev)
-    if (hipEventCreate(&x) != hipSuccess) { for (auto y : ev) if (y) (void)hipEventDestroy(y); set_err("event"); return FDGPU_ERR_DEVICE; }
-  /* a warm-up of both stages (it also leaves the roots the timed chains read: the fold is in place, so every timed
-     tree run starts from the leaves again), then iters trees between two events and iters chains between the next
-     two */
-  bool ok = b.tree(n, sig_total, st) && b.chains(n, hash_cnt_cap, 0, st) && hipEventRecord(ev[0], st) == hipSuccess;
-  for (int i = 0; i < iters && ok; i++) ok = b.tree(n, sig_total, st);
-  ok = ok && hipEventRecord(ev[1], st) == hipSuccess;
-  for (int i = 0; i < iters && ok; i++) ok = b.chains(n, hash_cnt_cap, 0, st);
-  ok = ok && hipEventRecord(ev[2], st) == hipSuccess && hipEventSynchronize(ev[2]) == hipSuccess;
-  float a = 0.f, c = 0.f;
-  ok = ok && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&c, ev[1], ev[2]) == hipSuccess;
-  for (auto x : ev) (void)hipEventDestroy(x);
-  if (!ok) { (void)hipGetLastError(); set_err("poh timing failed"); return FDGPU_ERR_DEVICE; }
-  *tree_ms = a / iters;
-  *chain_ms = c / iters;
-  return FDGPU_OK;
+  /* the warm-up also leaves the roots the timed chains read: the fold is in place, so every timed tree run starts
+     from the leaves again */
+  auto tree = [&] { return b.tree(n, sig_total, st); };
+  auto chains = [&] { return b.chains(n, hash_cnt_cap, 0, st); };
+  return time_two_stages(st, iters, "poh", [&] { return tree() && chains(); }, tree, chains, tree_ms, chain_ms);
 }
 
 }  // extern "C"

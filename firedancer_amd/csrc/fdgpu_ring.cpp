@@ -33,9 +33,13 @@ std::atomic<uint64_t> g_st_n{0};
 
 namespace fdgpu {
 
-Slot *free_slot(fdgpu_engine_t *e) {
-  for (auto &c : e->slots) if (c.ticket < 0 && !c.staged) return &c;
-  return nullptr;
+/* A free slot of the ring (ring_mu held), the engine's device made the thread's current one: FDGPU_OK and *s, or the
+   error with its text set. */
+int take_slot(fdgpu_engine_t *e, Slot **s) {
+  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
+  for (auto &c : e->slots) if (c.ticket < 0 && !c.staged) { *s = &c; return FDGPU_OK; }
+  set_err("all ring slots hold unpolled batches");
+  return FDGPU_ERR_FULL;
 }
 
 /* The end of a batch's work on its stream: the next sequence number, the completion word the stream writes after
@@ -72,7 +76,7 @@ int64_t slot_publish(fdgpu_engine_t *e, Slot *s, Batch kind, uint64_t txn_cnt, u
    rest of the staging (one core's memcpy bandwidth, ~15 GB/s, otherwise bounds submit()).  Returns the bytes already
    queued for upload, or UINT64_MAX on a HIP error.  An arena that expand() later rejects leaves the slot free; its
    stale upload is overwritten by the next batch's copies, which are ordered after it on the same stream. */
-uint64_t stage_arena(fdgpu_engine_t *e, Slot *s, uint8_t const *arena, uint64_t sz) {
+static uint64_t stage_arena(fdgpu_engine_t *e, Slot *s, uint8_t const *arena, uint64_t sz) {
   if (sz < FDGPU_COPY_SPLIT_MIN) {
     memcpy(s->h_arena, arena, sz);
     return 0;
@@ -100,6 +104,24 @@ uint64_t stage_arena(fdgpu_engine_t *e, Slot *s, uint8_t const *arena, uint64_t 
   for (unsigned i = 0; i < FDGPU_COPY_THREADS; i++)
     if (err[i]) { set_err("staging upload failed"); return UINT64_MAX; }
   return sz;
+}
+
+/* Queue the upload of a frag, shred or PoH batch's whole arena on the slot's stream: one copy straight from the
+   caller's memory where that lies in a registered region (its bytes must stay unchanged until the batch is polled),
+   else staged through the slot's pinned buffer.  The slack past the arena needs no zeroing: every device reader of
+   these batches masks the bytes past its item in registers (fdt_reader, msg_block, fdgpu_sha256.h), only their
+   presence (FDGPU_ARENA_SLACK allocated) matters. */
+int slot_upload(fdgpu_engine_t *e, Slot *s, uint8_t const *arena, uint64_t arena_sz) {
+  if (region_of(e, (uintptr_t)arena, arena_sz)) {
+    if (arena_sz) HIPCHK(hipMemcpyAsync(s->d_arena, arena, arena_sz, hipMemcpyHostToDevice, s->stream), FDGPU_ERR_DEVICE);
+    return FDGPU_OK;
+  }
+  const uint64_t up = stage_arena(e, s, arena, arena_sz);
+  if (up == UINT64_MAX) return FDGPU_ERR_DEVICE;
+  if (arena_sz > up)
+    HIPCHK(hipMemcpyAsync(s->d_arena + up, s->h_arena + up, arena_sz - up, hipMemcpyHostToDevice, s->stream),
+           FDGPU_ERR_DEVICE);
+  return FDGPU_OK;
 }
 
 }  // namespace fdgpu
@@ -247,12 +269,9 @@ int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking
       break;
     }
     case Batch::Shred:
-      if (txn_codes && n) memcpy(txn_codes, s->h_shres, n);
-      if (roots && n) memcpy(roots, s->h_shres + s->tr_base, n * 32);
-      break;
     case Batch::Poh:
-      if (txn_codes && n) memcpy(txn_codes, s->h_pres, n);
-      if (roots && n) memcpy(roots, s->h_pres + s->tr_base, n * 32);
+      if (txn_codes && n) memcpy(txn_codes, s->h_res, n);
+      if (roots && n) memcpy(roots, s->h_res + item_results(n).items, n * 32);
       break;
   }
   if (keep) st_rlx(s->held, true);
@@ -269,9 +288,10 @@ int64_t fdgpu_submit(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz,
   if (!e || (!arena && arena_sz) || (!txns && txn_cnt)) { set_err("null argument"); return FDGPU_ERR_INVAL; }
   if (arena_sz > e->cfg.max_arena || txn_cnt > e->cfg.max_txn) { set_err("batch exceeds engine limits"); return FDGPU_ERR_INVAL; }
   std::lock_guard<std::mutex> lk(e->ring_mu);
-  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
-  Slot *s = free_slot(e);
-  if (!s) { set_err("all ring slots hold unpolled batches"); return FDGPU_ERR_FULL; }
+  Slot *s = nullptr;
+  if (const int rc = take_slot(e, &s)) return rc;
+  /* not slot_upload: a staged arena's last copy carries the zeroed slack and is queued after the expansion, under
+     which the parts already queued run (submit_slot) */
   if (region_of(e, (uintptr_t)arena, arena_sz)) return submit_slot(e, s, arena_sz, txns, txn_cnt, 0, arena);
   /* the slot's previous batch was polled, so its copies are complete */
   const uint64_t ts = sp_now();
@@ -284,8 +304,8 @@ uint8_t *fdgpu_stage_acquire(fdgpu_engine_t *e, uint64_t *cap) {
   if (!e) return nullptr;
   std::lock_guard<std::mutex> lk(e->ring_mu);
   for (auto &c : e->slots) if (c.staged) { set_err("a slot is already staged"); return nullptr; }
-  Slot *s = free_slot(e);
-  if (!s) { set_err("all ring slots hold unpolled batches"); return nullptr; }
+  Slot *s = nullptr;
+  if (take_slot(e, &s)) return nullptr;
   s->staged = true;
   if (cap) *cap = e->cfg.max_arena;
   return s->h_arena;
@@ -366,12 +386,11 @@ uint64_t fdgpu_debug_submit_times(uint64_t *out, uint64_t max) {
 double fdgpu_debug_h2d_gbps(fdgpu_engine_t *e, void const *src, uint64_t sz, int iters) {
   if (!e || !src || !sz || iters < 1 || sz > e->cfg.max_arena) { set_err("bad argument"); return -1.0; }
   std::lock_guard<std::mutex> lk(e->ring_mu);
-  Slot *s = free_slot(e);
-  if (!s) { set_err("all ring slots hold unpolled batches"); return -1.0; }
-  HIPCHK(hipSetDevice(e->device), -1.0);
-  hipEvent_t a, b;
-  HIPCHK(hipEventCreate(&a), -1.0);
-  if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); set_err("event"); return -1.0; }
+  Slot *s = nullptr;
+  if (take_slot(e, &s)) return -1.0;
+  Events ev;
+  if (!ev.create(2)) { (void)hipGetLastError(); set_err("event"); return -1.0; }
+  const hipEvent_t a = ev[0], b = ev[1];
   double gbps = -1.0;
   float ms = 0.f;
   if (hipMemcpyAsync(s->d_arena, src, sz, hipMemcpyHostToDevice, s->stream) == hipSuccess &&   /* warm */
@@ -384,8 +403,6 @@ double fdgpu_debug_h2d_gbps(fdgpu_engine_t *e, void const *src, uint64_t sz, int
       gbps = (double)sz * iters / (ms * 1e-3) / 1e9;
   }
   (void)hipGetLastError();
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
   if (gbps < 0) set_err("h2d timing failed");
   return gbps;
 }

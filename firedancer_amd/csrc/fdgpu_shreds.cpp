@@ -10,10 +10,6 @@ using namespace fdgpu;
 
 namespace {
 
-/* the results of n shreds: [codes, padded to 64][32-B roots] */
-inline uint64_t res_roots(uint64_t n) { return (n + 63) & ~63ull; }
-inline uint64_t res_bytes(uint64_t n) { return res_roots(n) + 32 * n; }
-
 /* The roots region of a batch lies in the arena's own allocation, behind the payload and its slack, so that a
    signature descriptor's 32-bit offsets reach it and the verify reads the roots as it reads any message; `cap` is
    what the allocation holds besides its trailing FDGPU_ARENA_SLACK (which then lies behind the last root).  Checks
@@ -41,8 +37,6 @@ bool slot_shred_bufs(Slot &s, const fdgpu_cfg_t &c) {
   const uint64_t n = c.max_txn + 1;
   HIPCHK(s.h_sh.alloc(n * sizeof(fdgpu_shred_t)), false);
   HIPCHK(s.d_sh_cnt.alloc(64), false);
-  HIPCHK(s.d_shres.alloc(res_bytes(n)), false);
-  HIPCHK(s.h_shres.alloc(res_bytes(n)), false);
   HIPCHK(s.d_sh.alloc(n * sizeof(fdgpu_shred_t)), false);
   return true;
 }
@@ -61,16 +55,15 @@ struct DevShreds {
     const int rc = shred_args(e, a, arena_sz, s, n, UINT32_MAX - 64ull * 1024, &roots_off);
     if (rc) return rc;
     HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
-    const uint64_t bytes = roots_off + 32 * n + FDGPU_ARENA_SLACK;
-    if (arena.alloc(bytes) || res.alloc(res_bytes(n)) || sh.alloc(n * sizeof(fdgpu_shred_t)) ||
+    /* the roots region behind the arena and its slack, zeroed with them */
+    HIPCHK(dev_arena(arena, a, arena_sz, roots_off + 32 * n - arena_sz, false), FDGPU_ERR_DEVICE);
+    if (res.alloc(item_results(n).bytes) || sh.alloc(n * sizeof(fdgpu_shred_t)) ||
         sigs.alloc(n * sizeof(fdgpu_sig_desc_t) + 16) || tds.alloc(n * sizeof(fdgpu_txn_desc_t) + 16) || cnt.alloc(64) ||
         sig_codes.alloc(n + 16)) {
       (void)hipGetLastError();
       set_err("alloc");
       return FDGPU_ERR_DEVICE;
     }
-    HIPCHK(hipMemset(arena.p + arena_sz, 0, bytes - arena_sz), FDGPU_ERR_DEVICE);
-    if (arena_sz) HIPCHK(hipMemcpy(arena, a, arena_sz, hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
     HIPCHK(hipMemcpy(sh, s, n * sizeof(fdgpu_shred_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
     return FDGPU_OK;
   }
@@ -93,22 +86,12 @@ int64_t fdgpu_submit_shreds(fdgpu_engine_t *e, uint8_t const *arena, uint64_t ar
   const int arc = shred_args(e, arena, arena_sz, sh, n, e ? e->cfg.max_arena : 0, &roots_off);
   if (arc) return arc;
   std::lock_guard<std::mutex> lk(e->ring_mu);
-  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
-  Slot *s = free_slot(e);
-  if (!s) { set_err("all ring slots hold unpolled batches"); return FDGPU_ERR_FULL; }
+  Slot *s = nullptr;
+  if (const int rc = take_slot(e, &s)) return rc;
   if (!n) return slot_publish(e, s, Batch::Shred, 0, 0, 0);
-  if (!slot_shred_bufs(*s, e->cfg) || !slot_ws(*s, n)) return FDGPU_ERR_DEVICE;
-  /* the slack past the arena needs no zeroing: the leaf and proof loads that run past a shred are masked in
-     registers (fdgpu_sha256.h), only the bytes' presence matters */
-  if (region_of(e, (uintptr_t)arena, arena_sz)) {
-    if (arena_sz) HIPCHK(hipMemcpyAsync(s->d_arena, arena, arena_sz, hipMemcpyHostToDevice, s->stream), FDGPU_ERR_DEVICE);
-  } else {
-    const uint64_t up = stage_arena(e, s, arena, arena_sz);
-    if (up == UINT64_MAX) return FDGPU_ERR_DEVICE;
-    if (arena_sz > up)
-      HIPCHK(hipMemcpyAsync(s->d_arena + up, s->h_arena + up, arena_sz - up, hipMemcpyHostToDevice, s->stream),
-             FDGPU_ERR_DEVICE);
-  }
+  if (!slot_shred_bufs(*s, e->cfg) || !slot_res_bufs(*s, e->cfg) || !slot_ws(*s, n)) return FDGPU_ERR_DEVICE;
+  if (const int rc = slot_upload(e, s, arena, arena_sz)) return rc;
+  const ItemResults res = item_results(n);
   memcpy(s->h_sh, sh, n * sizeof(fdgpu_shred_t));
   HIPCHK(hipMemcpyAsync(s->d_sh, s->h_sh, n * sizeof(fdgpu_shred_t), hipMemcpyHostToDevice, s->stream), FDGPU_ERR_DEVICE);
   HIPCHK(hipMemsetAsync(s->d_sh_cnt, 0, sizeof(uint32_t), s->stream), FDGPU_ERR_DEVICE);
@@ -119,41 +102,15 @@ int64_t fdgpu_submit_shreds(fdgpu_engine_t *e, uint8_t const *arena, uint64_t ar
   HIPCHK(fdgpu_launch_verify_sigs(s->d_arena, s->d_sigs, (uint32_t)n, nullptr, e->d_btab, s->d_ws, s->d_sig_codes,
                                   ring_kflags(e, s, n), s->stream, s->d_sh_cnt, e->resident_blocks, e->kc_seed),
          FDGPU_ERR_DEVICE);
-  HIPCHK(fdgpu_launch_shred_finish(s->d_txns, (uint32_t)n, s->d_sig_codes, s->d_arena + roots_off, (int8_t *)s->d_shres.p,
-                                   s->d_shres + res_roots(n), s->stream),
+  HIPCHK(fdgpu_launch_shred_finish(s->d_txns, (uint32_t)n, s->d_sig_codes, s->d_arena + roots_off, (int8_t *)s->d_res.p,
+                                   s->d_res + res.items, s->stream),
          FDGPU_ERR_DEVICE);
-  HIPCHK(hipMemcpyAsync(s->h_shres, s->d_shres, res_bytes(n), hipMemcpyDeviceToHost, s->stream), FDGPU_ERR_DEVICE);
-  return slot_publish(e, s, Batch::Shred, n, 32 * n, res_roots(n));
+  HIPCHK(hipMemcpyAsync(s->h_res, s->d_res, res.bytes, hipMemcpyDeviceToHost, s->stream), FDGPU_ERR_DEVICE);
+  return slot_publish(e, s, Batch::Shred, n, 0, 0);
 }
 
 int fdgpu_poll_shreds(fdgpu_engine_t *e, int64_t ticket, int8_t *codes, uint8_t *roots, int blocking) {
   return poll_slot(e, ticket, codes, blocking, false, nullptr, nullptr, nullptr, roots);
-}
-
-int fdgpu_debug_sha256(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_txn_t const *msgs, uint64_t n,
-                       uint8_t *out) {
-  if (!e || !n || !msgs || !out || (!arena && arena_sz) || arena_sz > 0xFFFFFF00ull) { set_err("bad argument"); return FDGPU_ERR_INVAL; }
-  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
-  std::vector<fdgpu_sig_desc_t> d(n);
-  for (uint64_t i = 0; i < n; i++) {
-    if ((uint64_t)msgs[i].msg_off + msgs[i].msg_sz > arena_sz) { set_err("descriptor out of bounds"); return FDGPU_ERR_INVAL; }
-    d[i] = fdgpu_sig_desc_t{msgs[i].msg_off, msgs[i].msg_sz, 0, 0};
-  }
-  DevBuf<uint8_t> da;
-  DevBuf<fdgpu_sig_desc_t> dd;
-  DevBuf<uint32_t> dout;
-  if (da.alloc(arena_sz + FDGPU_ARENA_SLACK) || dd.alloc(n * sizeof(fdgpu_sig_desc_t)) || dout.alloc(n * 32)) {
-    (void)hipGetLastError();
-    set_err("alloc");
-    return FDGPU_ERR_DEVICE;
-  }
-  HIPCHK(hipMemset(da, 0, arena_sz + FDGPU_ARENA_SLACK), FDGPU_ERR_DEVICE);
-  if (arena_sz) HIPCHK(hipMemcpy(da, arena, arena_sz, hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
-  HIPCHK(hipMemcpy(dd, d.data(), n * sizeof(fdgpu_sig_desc_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
-  HIPCHK(fdgpu_launch_test_sha256(da, dd, (uint32_t)n, dout, e->compute), FDGPU_ERR_DEVICE);
-  HIPCHK(hipStreamSynchronize(e->compute), FDGPU_ERR_DEVICE);
-  HIPCHK(hipMemcpy(out, dout, n * 32, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
-  return FDGPU_OK;
 }
 
 int fdgpu_debug_shred_roots(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_shred_t const *sh,
@@ -164,11 +121,11 @@ int fdgpu_debug_shred_roots(fdgpu_engine_t *e, uint8_t const *arena, uint64_t ar
   if (!rc) rc = b.ingest(n, expected_version, e->compute);
   if (rc) return rc;
   HIPCHK(fdgpu_launch_shred_finish(b.tds, (uint32_t)n, nullptr, b.arena + b.roots_off, (int8_t *)b.res.p,
-                                   b.res + res_roots(n), e->compute),
+                                   b.res + item_results(n).items, e->compute),
          FDGPU_ERR_DEVICE);
   HIPCHK(hipStreamSynchronize(e->compute), FDGPU_ERR_DEVICE);
   HIPCHK(hipMemcpy(ok, b.res, n, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
-  HIPCHK(hipMemcpy(roots, b.res + res_roots(n), 32 * n, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(roots, b.res + item_results(n).items, 32 * n, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
   return FDGPU_OK;
 }
 
@@ -184,27 +141,13 @@ int fdgpu_debug_shred_time(fdgpu_engine_t *e, uint8_t const *arena, uint64_t are
     if (rc) return rc;
   }
   hipStream_t st = e->compute;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  for (auto &x : ev)
-    if (hipEventCreate(&x) != hipSuccess) { for (auto y : ev) if (y) (void)hipEventDestroy(y); set_err("event"); return FDGPU_ERR_DEVICE; }
-  /* a warm-up of both stages (it also leaves the descriptors and the count the timed verifies read), then iters
-     ingests between two events and iters verifies between the next two */
+  /* the warm-up also leaves the descriptors and the count the timed verifies read */
+  auto ingest = [&] { return !b.ingest(n, expected_version, st); };
   auto verify = [&] {
     return fdgpu_launch_verify_sigs(b.arena, b.sigs, (uint32_t)n, nullptr, e->d_btab, e->d_ws, b.sig_codes, kflags(e), st,
                                     b.cnt, e->resident_blocks, e->kc_seed) == hipSuccess;
   };
-  bool ok = !b.ingest(n, expected_version, st) && verify() && hipEventRecord(ev[0], st) == hipSuccess;
-  for (int i = 0; i < iters && ok; i++) ok = !b.ingest(n, expected_version, st);
-  ok = ok && hipEventRecord(ev[1], st) == hipSuccess;
-  for (int i = 0; i < iters && ok; i++) ok = verify();
-  ok = ok && hipEventRecord(ev[2], st) == hipSuccess && hipEventSynchronize(ev[2]) == hipSuccess;
-  float a = 0.f, v = 0.f;
-  ok = ok && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&v, ev[1], ev[2]) == hipSuccess;
-  for (auto x : ev) (void)hipEventDestroy(x);
-  if (!ok) { (void)hipGetLastError(); set_err("shred timing failed"); return FDGPU_ERR_DEVICE; }
-  *ingest_ms = a / iters;
-  *verify_ms = v / iters;
-  return FDGPU_OK;
+  return time_two_stages(st, iters, "shred", [&] { return ingest() && verify(); }, ingest, verify, ingest_ms, verify_ms);
 }
 
 }  // extern "C"
