@@ -170,6 +170,8 @@ def lib():
     L.fdgpu_debug_sc_recode.argtypes = [vp, vp, c.c_uint64, vp]
     L.fdgpu_debug_btab.argtypes = [vp, c.c_uint64, c.c_uint64, vp]
     L.fdgpu_debug_tabpack.argtypes = [vp, vp, c.c_uint64, vp]
+    L.fdgpu_debug_verify_prehashed.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint32, vp,
+                                               c.POINTER(c.c_uint32)]
     L.fdgpu_bcomb_dim.argtypes = [c.c_int]
     L.fdgpu_bcomb_dim.restype = c.c_uint32
     L.fdgpu_test_ge_in_words.argtypes = []
@@ -179,7 +181,7 @@ def lib():
     for fn in ("fdgpu_debug_fe_ops", "fdgpu_debug_decode", "fdgpu_debug_sha512", "fdgpu_debug_hram",
                "fdgpu_debug_sc_reduce", "fdgpu_debug_hs_split", "fdgpu_debug_sig_codes",
                "fdgpu_debug_fe_raw", "fdgpu_debug_ge_ops", "fdgpu_debug_sc_recode", "fdgpu_debug_btab",
-               "fdgpu_debug_tabpack"):
+               "fdgpu_debug_tabpack", "fdgpu_debug_verify_prehashed"):
         getattr(L, fn).restype = c.c_int
     _LIB = L
     return L

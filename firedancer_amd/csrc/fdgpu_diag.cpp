@@ -129,6 +129,37 @@ int fdgpu_debug_tabpack(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint8_
   return debug_map(e, in, n, FDGPU_ATAB_WORDS, FDGPU_TABPACK_OUT_WORDS, out, fdgpu_launch_test_tabpack);
 }
 
+int fdgpu_debug_verify_prehashed(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz,
+                                 fdgpu_sig_desc_t const *descs, uint64_t n, uint32_t flags, int8_t *codes_out,
+                                 uint32_t *n_full_out) {
+  if (!e || !e->d_btab || !arena || !descs || !codes_out || !n_full_out || !n || n > (1u << 20) ||
+      arena_sz > 0xFFFFFF00ull || (flags & ~(uint32_t)(FDGPU_FLAG_REF_MAP | FDGPU_FLAG_KFULL | FDGPU_FLAG_KPAIR))) {
+    set_err("fdgpu_debug_verify_prehashed: bad argument"); return FDGPU_ERR_INVAL;
+  }
+  for (uint64_t i = 0; i < n; i++) {
+    if ((descs[i].msg_off & 7u) || (uint64_t)descs[i].msg_off + 64 > arena_sz ||
+        (uint64_t)descs[i].sig_off + 64 > arena_sz || (uint64_t)descs[i].pub_off + 32 > arena_sz) {
+      set_err("fdgpu_debug_verify_prehashed: descriptor out of bounds"); return FDGPU_ERR_INVAL;
+    }
+  }
+  HIPCHK(hipSetDevice(e->device), FDGPU_ERR_DEVICE);
+  DevBuf<uint8_t> da;
+  DevBuf<fdgpu_sig_desc_t> dd;
+  DevBuf<int8_t> dc;
+  DevBuf<uint32_t> dws;
+  HIPCHK(dev_arena(da, arena, arena_sz), FDGPU_ERR_DEVICE);
+  DALLOC(dd, n);
+  DALLOC(dc, n);
+  if (dws.alloc(fdgpu_ws_bytes(n)) != hipSuccess) { set_err("alloc"); return FDGPU_ERR_DEVICE; }
+  HIPCHK(hipMemcpy(dd, descs, n * sizeof(fdgpu_sig_desc_t), hipMemcpyHostToDevice), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemsetAsync(dc, 0x7f, n, e->compute), FDGPU_ERR_DEVICE);   /* a code no kernel writes */
+  HIPCHK(fdgpu_launch_verify_prehashed(da, dd, (uint32_t)n, e->d_btab, dws, dc, flags, e->compute), FDGPU_ERR_DEVICE);
+  HIPCHK(hipStreamSynchronize(e->compute), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(codes_out, dc, n, hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
+  HIPCHK(hipMemcpy(n_full_out, fdgpu_ws_layout(dws, n).cnt, sizeof(uint32_t), hipMemcpyDeviceToHost), FDGPU_ERR_DEVICE);
+  return FDGPU_OK;
+}
+
 int fdgpu_debug_btab(fdgpu_engine_t *e, uint64_t first_entry, uint64_t n_entries, uint32_t *out) {
   const uint64_t total = (uint64_t)FDGPU_BCOMB_NDIG * FDGPU_BCOMB_ENTRIES;
   if (!e || !e->d_btab || !out || first_entry > total || n_entries > total - first_entry) {

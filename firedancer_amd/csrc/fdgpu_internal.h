@@ -167,7 +167,9 @@ hipError_t fdgpu_launch_verify_sigs(const uint8_t *d_arena, const fdgpu_sig_desc
    (blocks [blk0, blk0 + nblk) of fdgpu_sha512_stream_blocks(msg_sz); d_mbuf
    = M[m0, m0 + mlen) covering those blocks' message bytes; d_ra = n x (R ||
    A); d_state = n x 8 words), then the verify from those states
-   (descriptor i: msg_off = the offset of state i in d_arena, 8-B aligned). */
+   (descriptor i: msg_off = the offset of state i in d_arena, 8-B aligned;
+   of flags FDGPU_FLAG_REF_MAP, FDGPU_FLAG_KFULL and FDGPU_FLAG_KPAIR are
+   read, the last two for the chain diagnostic). */
 uint64_t   fdgpu_sha512_stream_blocks(uint64_t msg_sz);
 hipError_t fdgpu_launch_sha512_stream(const uint8_t *d_mbuf, uint64_t m0, uint64_t mlen, uint64_t msg_sz,
                                       uint64_t blk0, uint32_t nblk, const uint8_t *d_ra, uint64_t *d_state,
@@ -345,6 +347,14 @@ int      fdgpu_debug_sc_recode(fdgpu_engine_t *e, uint8_t const *s, uint64_t n, 
 /* n cached entries (40 u32 raw limbs each: Y+X, Y-X, 2Z, 2dT) through the table's store, load and LDS
    path; FDGPU_TABPACK_OUT_WORDS u32 per entry out */
 int      fdgpu_debug_tabpack(fdgpu_engine_t *e, uint8_t const *in, uint64_t n, uint8_t *out);
+/* the verify chain at chosen k (tests/test_gpu_chain.py): n descriptors whose msg_off is the offset (8-B
+   aligned) of 64 B of SHA-512 state words in the arena, as the synchronous API's over-arena path lays them
+   out, through fdgpu_launch_verify_prehashed with a workspace of its own; flags of FDGPU_FLAG_REF_MAP,
+   FDGPU_FLAG_KFULL (every lane queued) and FDGPU_FLAG_KPAIR (the two-lane kernel).  Descriptor i is lane i.
+   codes_out: n codes; *n_full_out: the fallback queue's count once the stream has drained */
+int      fdgpu_debug_verify_prehashed(fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz,
+                                      fdgpu_sig_desc_t const *descs, uint64_t n, uint32_t flags, int8_t *codes_out,
+                                      uint32_t *n_full_out);
 /* n_entries x FDGPU_BCOMB_STRIDE words of the engine's fixed-base table, from entry first_entry of the
    flat (table, entry) order, to the host; no kernel runs */
 int      fdgpu_debug_btab(fdgpu_engine_t *e, uint64_t first_entry, uint64_t n_entries, uint32_t *out);

@@ -678,6 +678,9 @@ FDG_DEV void fe_xchg_pair(fe &r, const fe &a) {
   for (int j = 0; j < 10; j++) r.v[j] = (uint32_t)__shfl_xor((int)a.v[j], 1);
 }
 
+/* PH: k from the lane's SHA-512 state words at msg_off, as in verify_hs_body
+   (the chain diagnostic's instantiation; the product's has PH false) */
+template <bool PH = false>
 __global__ void __launch_bounds__(FDGPU_BLOCK, FDGPU_VERIFY_WAVES)
 fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc_t *__restrict__ sigs, uint32_t n_sig_arg,
                          const uint32_t *__restrict__ n_sig_dev, const uint32_t *__restrict__ btab,
@@ -698,7 +701,17 @@ fdgpu_verify_pair_kernel(const uint8_t *__restrict__ arena, const fdgpu_sig_desc
   load32(Renc, arena + d.sig_off);
   load32(Aenc, arena + d.pub_off);
   uint32_t k[8];
-  hram_k(k, Renc, Aenc, arena, d, nb);
+  if (PH) {
+    uint32_t kx[16];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const uint64_t h = ((const uint64_t *)(arena + d.msg_off))[j];
+      kx[2 * j] = bswap32((uint32_t)(h >> 32)); kx[2 * j + 1] = bswap32((uint32_t)h);
+    }
+    sc_reduce512(k, kx);
+  } else {
+    hram_k(k, Renc, Aenc, arena, d, nb);
+  }
   uint32_t S[8];
   load32(S, arena + d.sig_off + 32);
   int code = sc_lt_L(S) ? 0 : -1;
@@ -1017,7 +1030,7 @@ hipError_t fdgpu_launch_verify_sigs(const uint8_t *d_arena, const fdgpu_sig_desc
     key_of = l.key_of;
   } else if (flags & FDGPU_FLAG_KPAIR) {
     const uint32_t pgrid = (2u * n_sig + FDGPU_BLOCK - 1) / FDGPU_BLOCK;     /* two lanes per signature */
-    hipLaunchKernelGGL(fdgpu_verify_pair_kernel, dim3(pgrid), dim3(FDGPU_BLOCK),
+    hipLaunchKernelGGL(fdgpu_verify_pair_kernel<false>, dim3(pgrid), dim3(FDGPU_BLOCK),
                        (flags & FDGPU_FLAG_KSPREAD) ? FDGPU_SPREAD_LDS_PAIR : 0, stream, d_arena, d_sigs, n_sig,
                        d_n_sig, d_btab, d_ws, d_perm, d_sig_codes, l.queue, l.cnt, flags);
   } else {
@@ -1049,9 +1062,17 @@ hipError_t fdgpu_launch_verify_prehashed(const uint8_t *d_arena, const fdgpu_sig
   const fdgpu_ws_layout_t l = fdgpu_ws_layout(d_ws, n_sig);
   hipError_t e = hipMemsetAsync(l.cnt, 0, sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((fdgpu_verify_hs_kernel<false, true>), dim3(grid), dim3(FDGPU_BLOCK), 0, stream, d_arena, d_sigs,
-                     n_sig, nullptr, d_btab, d_ws, nullptr, d_sig_codes, l.queue, l.cnt, flags & FDGPU_FLAG_REF_MAP,
-                     nullptr, nullptr);
+  /* the flags the prehashed kernels read; FDGPU_FLAG_KFULL and FDGPU_FLAG_KPAIR come only from the chain
+     diagnostic (fdgpu_debug_verify_prehashed): the synchronous path passes neither */
+  const uint32_t kf = flags & (FDGPU_FLAG_REF_MAP | FDGPU_FLAG_KFULL);
+  if (flags & FDGPU_FLAG_KPAIR) {
+    const uint32_t pgrid = (2u * n_sig + FDGPU_BLOCK - 1) / FDGPU_BLOCK;     /* two lanes per signature */
+    hipLaunchKernelGGL(fdgpu_verify_pair_kernel<true>, dim3(pgrid), dim3(FDGPU_BLOCK), 0, stream, d_arena, d_sigs,
+                       n_sig, nullptr, d_btab, d_ws, nullptr, d_sig_codes, l.queue, l.cnt, kf);
+  } else {
+    hipLaunchKernelGGL((fdgpu_verify_hs_kernel<false, true>), dim3(grid), dim3(FDGPU_BLOCK), 0, stream, d_arena, d_sigs,
+                       n_sig, nullptr, d_btab, d_ws, nullptr, d_sig_codes, l.queue, l.cnt, kf, nullptr, nullptr);
+  }
   hipLaunchKernelGGL(fdgpu_full_kernel, dim3(1), dim3(FDGPU_BLOCK), 0, stream, d_ws, nullptr, d_sig_codes, l.queue,
                      l.cnt, FDGPU_BLOCK, nullptr);
   return hipGetLastError();

@@ -35,6 +35,8 @@ TXN_DTYPE = np.dtype([("msg_off", "<u4"), ("msg_sz", "<u4"), ("sig_off", "<u4"),
                       ("pub_off", "<u4"), ("sig_cnt", "<u4")])
 SIG_DESC_DTYPE = np.dtype([("msg_off", "<u4"), ("msg_sz", "<u4"), ("sig_off", "<u4"), ("pub_off", "<u4")])
 TXN_DESC_DTYPE = np.dtype([("sig0", "<u4"), ("sig_cnt", "<u4")])
+# the kernels' flags debug_verify_prehashed passes (csrc/fdgpu_internal.h: FDGPU_FLAG_REF_MAP, _KFULL, _KPAIR)
+KFLAG_REF_MAP, KFLAG_FULL, KFLAG_PAIR = 1, 2, 8
 ARENA_SLACK = 160
 SHRED_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("pub_off", "<u4")])   # fdgpu_shred_t
 CODE_SHRED_REJECT = -67       # FDGPU_CODE_SHRED_REJECT
@@ -497,6 +499,22 @@ class VerifyEngine:
         out = np.zeros((len(ent), 160), dtype=np.uint32)
         self._chk(_lib.lib().fdgpu_debug_tabpack(self._h, ent.ctypes.data, len(ent), out.ctypes.data), "debug_tabpack")
         return out[:, :32].copy(), out[:, 32:152].reshape(-1, 3, 40).copy()
+
+    def debug_verify_prehashed(self, arena, descs, full=False, pair=False, ref_mapping=False):
+        """The verify chain at chosen k: descs (SIG_DESC_DTYPE, descriptor i =
+        lane i) whose msg_off is the 8-B aligned offset of 64 B of SHA-512
+        state words in arena, through the prehashed verify launch.  full:
+        every lane through the fallback; pair: the two-lane kernel.
+        -> (int8[n] codes, the fallback queue's final count)"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        descs = np.ascontiguousarray(descs, dtype=SIG_DESC_DTYPE)
+        codes = np.zeros(len(descs), dtype=np.int8)
+        n_full = ctypes.c_uint32(0)
+        flags = (KFLAG_REF_MAP if ref_mapping else 0) | (KFLAG_FULL if full else 0) | (KFLAG_PAIR if pair else 0)
+        self._chk(_lib.lib().fdgpu_debug_verify_prehashed(self._h, arena.ctypes.data, arena.size, descs.ctypes.data,
+                                                          len(descs), flags, codes.ctypes.data, ctypes.byref(n_full)),
+                  "debug_verify_prehashed")
+        return codes, int(n_full.value)
 
     def debug_btab(self):
         """The engine's fixed-base comb table -> uint32[NDIG, entries, stride]"""
