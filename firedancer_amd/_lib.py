@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("FDGPU_LIB") or os.path.join(_HERE, "libfd_ed25519_gpu
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_ed25519_gpu.h")
 SHRED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_shred_gpu.h")
 POH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_poh_gpu.h")
+PRECOMPILE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_precompile_gpu.h")
 
 _LIB = None
 
@@ -164,6 +165,19 @@ def lib():
     L.fdgpu_debug_poh_time.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, vp, c.c_uint64, c.c_uint64, c.c_int,
                                        c.POINTER(c.c_double), c.POINTER(c.c_double)]
     L.fdgpu_debug_poh_time.restype = c.c_int
+    # include/fd_precompile_gpu.h
+    L.fdgpu_precompile_sig_bound.argtypes = [c.c_uint64]
+    L.fdgpu_precompile_sig_bound.restype = c.c_uint32
+    L.fdgpu_submit_precompiles.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64]
+    L.fdgpu_submit_precompiles.restype = c.c_int64
+    L.fdgpu_poll_precompiles.argtypes = [vp, c.c_int64, vp, vp, c.c_int]
+    L.fdgpu_poll_precompiles.restype = c.c_int
+    L.fdgpu_debug_precompile_walk.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, vp, vp, vp, c.c_uint64,
+                                              c.POINTER(c.c_uint64)]
+    L.fdgpu_debug_precompile_walk.restype = c.c_int
+    L.fdgpu_debug_precompile_time.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_int, c.POINTER(c.c_double),
+                                              c.POINTER(c.c_double)]
+    L.fdgpu_debug_precompile_time.restype = c.c_int
     # the group layer's diagnostics (csrc/fdgpu_internal.h)
     L.fdgpu_debug_fe_raw.argtypes = [vp, vp, c.c_uint64, vp]
     L.fdgpu_debug_ge_ops.argtypes = [vp, vp, c.c_uint64, vp]

@@ -1,8 +1,8 @@
 /* fdgpu_engine.h -- what the host engine's units share (fdgpu_engine.cpp, fdgpu_ring.cpp, fdgpu_frags.cpp,
-   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp, fdgpu_shreds.cpp, fdgpu_poh_batch.cpp): the error text, the environment switches,
+   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp, fdgpu_shreds.cpp, fdgpu_poh_batch.cpp, fdgpu_precompiles.cpp): the error text, the environment switches,
    the owners of HIP memory, the ring's slot and the engine, the host-side buffer layouts, and the few internals more
    than one unit calls.  Everything here has hidden visibility: the exported C ABI is include/fd_ed25519_gpu.h and its
-   extensions include/fd_shred_gpu.h and include/fd_poh_gpu.h, nothing else (tests/test_abi.py).  The kernels do not include this file. */
+   extensions include/fd_shred_gpu.h, include/fd_poh_gpu.h and include/fd_precompile_gpu.h, nothing else (tests/test_abi.py).  The kernels do not include this file. */
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 
 #include "../../include/fd_ed25519_gpu.h"
 #include "../../include/fd_poh_gpu.h"
+#include "../../include/fd_precompile_gpu.h"
 #include "../../include/fd_shred_gpu.h"
 #include "fdgpu_internal.h"
 #include "fdt_parse.h"
@@ -157,12 +158,12 @@ inline IoResults io_results(uint64_t n) {
   return {cb, cb + n * 8, cb + n * 10};
 }
 
-/* An item batch's results for n items (a shred's root, a PoH entry's hash), in the slot's d_res and its pinned
-   read-back h_res: [codes, padded to 64][32 B per item]. */
+/* An item batch's results for n items (a shred's root, a PoH entry's hash: 32 B; a precompile transaction's info:
+   16 B), in the slot's d_res and its pinned read-back h_res: [codes, padded to 64][item_sz B per item]. */
 struct ItemResults { uint64_t items, bytes; };
-inline ItemResults item_results(uint64_t n) {
+inline ItemResults item_results(uint64_t n, uint64_t item_sz = 32) {
   const uint64_t cb = (n + 63) & ~63ull;
-  return {cb, cb + n * 32};
+  return {cb, cb + n * item_sz};
 }
 
 /* A gathered batch's pinned record area for n frags (h_io, read in place by the ingest kernel), each part 64-B
@@ -183,6 +184,7 @@ enum class Batch : uint8_t {
   FragIo,   /* fdgpu_submit_frags_io: io_results() in h_tr */
   Shred,    /* fdgpu_submit_shreds: item_results() in h_res, the items the roots */
   Poh,      /* fdgpu_submit_poh: item_results() in h_res, the items the hashes */
+  Precompile,   /* fdgpu_submit_precompiles: item_results(n, 16) in h_res, the items the infos */
 };
 
 struct Slot {
@@ -231,8 +233,8 @@ struct Slot {
                                                  engines, parsed and verified in place (the batch arena) */
   uint64_t mirror_cap = 0;
   uint8_t *d_trh = nullptr;                   /* h_tr's device-side address (results written in place) */
-  /* shred and PoH batches: item_results() of max_txn + 1 items and their pinned read-back, allocated on the slot's
-     first batch of either kind (slot_res_bufs) */
+  /* shred, PoH and precompile batches: item_results() of max_txn + 1 items (32 B each, which holds a precompile
+     batch's 16) and their pinned read-back, allocated on the slot's first batch of any of them (slot_res_bufs) */
   DevBuf<uint8_t> d_res; HostBuf<uint8_t> h_res;
   /* shred batches (fdgpu_submit_shreds), allocated on the slot's first one for max_txn shreds: the records and the
      ingest's signature count */
@@ -243,6 +245,13 @@ struct Slot {
      tree's nodes (32 B per signature) */
   HostBuf<fdgpu_poh_entry_t> h_pe; DevBuf<fdgpu_poh_entry_t> d_pe;
   HostBuf<uint32_t> h_psig, h_pord; DevBuf<uint32_t> d_psig, d_pord, d_pnodes, d_phead;
+  /* precompile batches (fdgpu_submit_precompiles), allocated on the slot's first one for max_txn transactions and
+     max_sig signatures: the records, the ingest's signature count, the parsed fd_txn_t records (FDT_TXN_MAX_SZ_BYTES
+     each), the walks' outcomes and the signatures' positions */
+  HostBuf<fdgpu_precompile_t> h_pc; DevBuf<fdgpu_precompile_t> d_pc;
+  DevBuf<uint32_t> d_pc_cnt, d_pc_pos;
+  DevBuf<uint8_t> d_pc_txn;
+  DevBuf<fdgpu_precompile_walk_t> d_pc_walk;
   /* FDGPU_FLAG_MERGE: the batch's gather + parse are queued and its verify waits to be merged with the other batches
      ready (merge_kick), which then queues the rest of the batch behind it */
   hipEvent_t parsed = nullptr;
@@ -335,9 +344,10 @@ int slot_upload(fdgpu_engine_t *e, Slot *s, uint8_t const *arena, uint64_t arena
 int slot_signal(fdgpu_engine_t *e, Slot *s);
 int64_t slot_publish(fdgpu_engine_t *e, Slot *s, Batch kind, uint64_t txn_cnt, uint64_t tr_sz, uint64_t tr_base,
                      bool signal_deferred = false);
-/* the poll of every batch kind: what the kind does not produce stays unwritten */
+/* the poll of every batch kind: what the kind does not produce stays unwritten (items: a shred batch's roots, a PoH
+   batch's hashes, a precompile batch's infos) */
 int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking, bool keep, uint8_t *trailers = nullptr,
-              uint64_t *tags = nullptr, uint16_t *out_szs = nullptr, uint8_t *roots = nullptr);
+              uint64_t *tags = nullptr, uint16_t *out_szs = nullptr, uint8_t *items = nullptr);
 
 /* fdgpu_frags.cpp */
 int merge_kick(fdgpu_engine_t *e, bool force);

@@ -194,7 +194,7 @@ int64_t submit_slot(fdgpu_engine_t *e, Slot *s, uint64_t arena_sz, fdgpu_txn_t c
 namespace fdgpu {
 
 int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking, bool keep, uint8_t *trailers,
-              uint64_t *tags, uint16_t *out_szs, uint8_t *roots) {
+              uint64_t *tags, uint16_t *out_szs, uint8_t *items) {
   if (!e) return FDGPU_ERR_INVAL;
   /* a batch still on the device is answered without the ring lock: the caller owns its ticket's slot until a poll
      returns it done, so the slot's ticket and completion word are stable here; the runtime check below (every 256th
@@ -271,7 +271,11 @@ int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking
     case Batch::Shred:
     case Batch::Poh:
       if (txn_codes && n) memcpy(txn_codes, s->h_res, n);
-      if (roots && n) memcpy(roots, s->h_res + item_results(n).items, n * 32);
+      if (items && n) memcpy(items, s->h_res + item_results(n).items, n * 32);
+      break;
+    case Batch::Precompile:
+      if (txn_codes && n) memcpy(txn_codes, s->h_res, n);
+      if (items && n) memcpy(items, s->h_res + item_results(n, 16).items, n * 16);
       break;
   }
   if (keep) st_rlx(s->held, true);

@@ -18,7 +18,15 @@
               the Merkle root of its signatures and mixes it in;
               fdgpu_block_poh_verify takes the entries of many blocks and
               their raw transactions and runs them as PoH batches on the
-              engine (fd_poh_gpu.h), fdgpu_poh_verify_host on the host.
+              engine (fd_poh_gpu.h), fdgpu_poh_verify_host on the host;
+     precompiles  fd_executor_verify_precompiles (src/flamenco/runtime/
+              fd_executor.c:252-270) walks each transaction's Ed25519
+              precompile instructions and runs fd_ed25519_verify on every
+              record of their tables; fdgpu_precompiles_verify walks on the
+              host (fdt_precompile.h) and verifies the records in batches,
+              fdgpu_block_precompile_verify sends a block's transactions
+              that carry such instructions through the engine
+              (fd_precompile_gpu.h).
 
    Both cut the work into batches within the verifier's limits, keep up to
    two batches in flight (the next one is staged while the GPU runs the
@@ -32,6 +40,7 @@
 
 #include "../../../include/fd_verify_tile.h"
 #include "../fdt_poh.h"
+#include "../fdt_precompile.h"
 #include "../fdt_shred.h"
 
 namespace {
@@ -379,6 +388,233 @@ int fdgpu_block_poh_verify(fdgpu_engine_t *e, const uint8_t in_hash[32], const u
     }
     c->en.push_back(d);
     c->items.push_back(i);
+  }
+  if (!r) r = submit(*c);
+  while (cnt) {                                /* on an error too: no batch is left in the ring */
+    const int d = drain_one();
+    if (d) return r ? r : d;
+  }
+  return r;
+}
+
+}  // extern "C"
+
+/* ---- precompiles ---- */
+
+namespace {
+
+struct rec_store {
+  fdt_precompile_rec_t *recs;
+  uint32_t cap, n = 0;
+  void operator()(uint32_t j, uint32_t i, uint32_t sig_at, uint32_t pub_at, uint32_t msg_at, uint32_t msg_sz) {
+    if (n < cap) recs[n] = {(uint16_t)j, (uint16_t)i, (uint16_t)sig_at, (uint16_t)pub_at, (uint16_t)msg_at, (uint16_t)msg_sz};
+    n++;
+  }
+};
+
+/* fn(i) for i in [0, n) on up to 16 threads, dealt in runs of 256 */
+template <class Fn> void par_for(uint64_t n, Fn fn) {
+  std::atomic<uint64_t> next{0};
+  auto work = [&] {
+    for (uint64_t b; (b = next.fetch_add(256)) < n;)
+      for (uint64_t i = b; i < std::min(n, b + 256); i++) fn(i);
+  };
+  const unsigned hw = std::thread::hardware_concurrency();
+  const uint64_t nt = std::min<uint64_t>({16, hw ? hw : 1, (n + 1023) / 1024});
+  std::vector<std::thread> th;
+  for (uint64_t t = 1; t < nt; t++) th.emplace_back(work);
+  work();
+  for (auto &t : th) t.join();
+}
+
+const fdgpu_precompile_info_t INFO_NONE = {0xFFFF, 0xFFFF, 0, 0, 0, {0, 0, 0, 0, 0, 0, 0}};
+
+}  // namespace
+
+extern "C" {
+
+void fdt_precompile_walk(const uint8_t *payload, uint64_t sz, const void *txn, fdt_precompile_rec_t *recs, uint32_t rec_cap,
+                         fdt_precompile_walk_t *out) {
+  rec_store st{recs, recs ? rec_cap : 0u};
+  fdt_precompile_walk_core(payload, sz, (const fdt_txn_t *)txn, st, out);
+}
+
+int fdt_precompile_verdict(const fdt_precompile_walk_t *walk, const fdt_precompile_rec_t *recs, const int8_t *ed_codes,
+                           fdgpu_precompile_info_t *info) {
+  fdgpu_precompile_info_t tmp;
+  return fdt_precompile_verdict_core(
+      walk->code, walk->instr_idx, walk->rec_idx, walk->ed_instr_cnt, walk->rec_cnt,
+      [&](uint32_t k) { return (int)ed_codes[k]; },
+      [&](uint32_t k) { return ((uint32_t)recs[k].instr_idx << 16) | recs[k].rec_idx; }, info ? info : &tmp);
+}
+
+int fdgpu_precompiles_verify(fdgpu_verifier_t v, const uint8_t *payloads, const uint64_t *off, const uint32_t *sz,
+                             uint64_t n, uint64_t batch_max, int8_t *codes, fdgpu_precompile_info_t *info) {
+  if (!v.submit || !v.poll || !codes || (n && (!payloads || !off || !sz)) || !batch_max) return FDGPU_ERR_INVAL;
+  /* the walks first: a pass that counts each transaction's records, then one that stores them at their place */
+  std::vector<fdt_precompile_walk_t> walk(std::max<uint64_t>(n, 1));
+  std::vector<uint8_t> parsed(std::max<uint64_t>(n, 1));
+  std::vector<uint64_t> rec0(n + 1, 0);
+  auto one = [&](uint64_t i, fdt_precompile_rec_t *recs, uint32_t cap) {
+    alignas(8) uint8_t txn_buf[FDT_TXN_MAX_SZ];
+    const uint8_t *raw = payloads + off[i];
+    parsed[i] = sz[i] <= FDT_TXN_MTU && fdt_txn_parse(raw, sz[i], txn_buf, nullptr) != 0;
+    if (parsed[i]) fdt_precompile_walk(raw, sz[i], txn_buf, recs, cap, &walk[i]);
+    else walk[i] = {FDGPU_CODE_PARSE_FAIL, 0, 0xFFFF, 0xFFFF, 0, 0};
+  };
+  par_for(n, [&](uint64_t i) { one(i, nullptr, 0); });
+  for (uint64_t i = 0; i < n; i++) rec0[i + 1] = rec0[i] + walk[i].rec_cnt;
+  const uint64_t total = rec0[n];
+  std::vector<fdt_precompile_rec_t> recs(std::max<uint64_t>(total, 1));
+  par_for(n, [&](uint64_t i) { if (walk[i].rec_cnt) one(i, recs.data() + rec0[i], walk[i].rec_cnt); });
+  /* every record is one single-signature item: sig[64] | pub[32] | msg */
+  std::vector<int8_t> ed(std::max<uint64_t>(total, 1));
+  Pipe p(v, ed.data());
+  Chunk *c = nullptr;
+  int r = p.next(&c);
+  for (uint64_t i = 0; i < n && !r; i++) {
+    const uint8_t *raw = payloads + off[i];
+    for (uint64_t k = rec0[i]; k < rec0[i + 1]; k++) {
+      if (c->txns.size() == batch_max) {
+        r = p.submit(*c);
+        if (!r) r = p.next(&c);
+        if (r) break;
+      }
+      const fdt_precompile_rec_t &q = recs[k];
+      const uint32_t base = (uint32_t)c->arena.size();
+      c->arena.insert(c->arena.end(), raw + q.sig_off, raw + q.sig_off + 64);
+      c->arena.insert(c->arena.end(), raw + q.pub_off, raw + q.pub_off + 32);
+      c->arena.insert(c->arena.end(), raw + q.msg_off, raw + q.msg_off + q.msg_sz);
+      fdgpu_txn_t d;
+      d.sig_off = base;
+      d.pub_off = base + 64;
+      d.msg_off = base + 96;
+      d.msg_sz = q.msg_sz;
+      d.sig_cnt = 1;
+      c->txns.push_back(d);
+      c->items.push_back(k);
+    }
+  }
+  if (!r) r = p.submit(*c);
+  if (!r) r = p.finish();
+  if (r) return r;
+  for (uint64_t i = 0; i < n; i++) {
+    fdgpu_precompile_info_t tmp;
+    fdgpu_precompile_info_t *o = info ? info + i : &tmp;
+    if (!parsed[i]) { codes[i] = FDGPU_CODE_PARSE_FAIL; *o = INFO_NONE; continue; }
+    codes[i] = (int8_t)fdt_precompile_verdict(&walk[i], recs.data() + rec0[i], ed.data() + rec0[i], o);
+  }
+  return 0;
+}
+
+int fdgpu_block_precompile_verify(fdgpu_engine_t *e, fdgpu_verifier_t v_host, const uint8_t *payloads, const uint64_t *off,
+                                  const uint32_t *sz, uint64_t n_txn, uint64_t batch_txn_max, int8_t *codes,
+                                  fdgpu_precompile_info_t *info) {
+  if (!codes || !batch_txn_max || (n_txn && (!payloads || !off || !sz))) return FDGPU_ERR_INVAL;
+  if (!e && (!v_host.submit || !v_host.poll)) return FDGPU_ERR_INVAL;
+  /* the host's part: which transactions carry an Ed25519 instruction, and how many signature slots each needs */
+  std::vector<uint32_t> cap(std::max<uint64_t>(n_txn, 1));
+  std::vector<uint8_t> fwd(std::max<uint64_t>(n_txn, 1));
+  par_for(n_txn, [&](uint64_t i) {
+    alignas(8) uint8_t txn_buf[FDT_TXN_MAX_SZ];
+    const uint8_t *raw = payloads + off[i];
+    fwd[i] = 0;
+    if (sz[i] > FDT_TXN_MTU || !fdt_txn_parse(raw, sz[i], txn_buf, nullptr)) {
+      codes[i] = FDGPU_CODE_PARSE_FAIL;
+      if (info) info[i] = INFO_NONE;
+      return;
+    }
+    fdt_precompile_walk_t w;
+    fdt_precompile_walk(raw, sz[i], txn_buf, nullptr, 0, &w);
+    if (!w.ed_instr_cnt) {
+      codes[i] = 0;
+      if (info) info[i] = INFO_NONE;
+      return;
+    }
+    fwd[i] = 1;
+    cap[i] = w.rec_cnt;
+  });
+  std::vector<uint64_t> idx;
+  for (uint64_t i = 0; i < n_txn; i++) if (fwd[i]) idx.push_back(i);
+  if (idx.empty()) return 0;
+  if (!e) {
+    std::vector<uint64_t> o2(idx.size());
+    std::vector<uint32_t> s2(idx.size());
+    std::vector<int8_t> c2(idx.size());
+    std::vector<fdgpu_precompile_info_t> i2(idx.size());
+    for (size_t k = 0; k < idx.size(); k++) { o2[k] = off[idx[k]]; s2[k] = sz[idx[k]]; }
+    const int r = fdgpu_precompiles_verify(v_host, payloads, o2.data(), s2.data(), idx.size(), batch_txn_max, c2.data(),
+                                           i2.data());
+    if (r) return r;
+    for (size_t k = 0; k < idx.size(); k++) { codes[idx[k]] = c2[k]; if (info) info[idx[k]] = i2[k]; }
+    return 0;
+  }
+  uint64_t txn_max = 0, sig_max = 0, arena_max = 0;
+  if (fdgpu_poh_limits(e, &txn_max, &sig_max, &arena_max)) return FDGPU_ERR_INVAL;
+  txn_max = std::min(txn_max, batch_txn_max);
+  /* a batch: the forwarded payloads copied into an arena of the batch's own */
+  struct PcChunk {
+    std::vector<uint8_t> arena;
+    std::vector<fdgpu_precompile_t> tx;
+    std::vector<uint64_t> items;   /* caller's index of each transaction */
+    uint64_t cap = 0;
+    int64_t ticket = -1;
+  } slot[2];
+  int head = 0, cnt = 0;
+  std::vector<int8_t> buf;
+  std::vector<fdgpu_precompile_info_t> ibuf;
+  auto drain_one = [&]() -> int {
+    PcChunk &c = slot[head];
+    buf.resize(std::max<size_t>(c.tx.size(), 1));
+    ibuf.resize(std::max<size_t>(c.tx.size(), 1));
+    const int r = fdgpu_poll_precompiles(e, c.ticket, buf.data(), ibuf.data(), 1);
+    if (r != FDGPU_OK) return r < 0 ? r : FDGPU_ERR_DEVICE;
+    for (size_t i = 0; i < c.items.size(); i++) { codes[c.items[i]] = buf[i]; if (info) info[c.items[i]] = ibuf[i]; }
+    head ^= 1;
+    cnt--;
+    return 0;
+  };
+  auto next = [&](PcChunk **out) -> int {      /* the chunk to fill next (drains the oldest when both are busy) */
+    if (cnt == 2) {
+      const int r = drain_one();
+      if (r) return r;
+    }
+    PcChunk &c = slot[(head + cnt) & 1];
+    c.arena.clear(); c.tx.clear(); c.items.clear(); c.cap = 0;
+    *out = &c;
+    return 0;
+  };
+  auto submit = [&](PcChunk &c) -> int {
+    if (c.tx.empty()) return 0;
+    int64_t tk;
+    while ((tk = fdgpu_submit_precompiles(e, c.arena.data(), c.arena.size(), c.tx.data(), c.tx.size())) == FDGPU_ERR_FULL) {
+      if (!cnt) return FDGPU_ERR_FULL;
+      const int r = drain_one();
+      if (r) return r;
+    }
+    if (tk < 0) return (int)tk;
+    c.ticket = tk;
+    cnt++;
+    return 0;
+  };
+  PcChunk *c = nullptr;
+  int r = next(&c);
+  for (size_t k = 0; k < idx.size() && !r; k++) {
+    const uint64_t i = idx[k];
+    if (cap[i] > sig_max || sz[i] > arena_max) { r = FDGPU_ERR_INVAL; break; }   /* one transaction no batch can hold */
+    if (c->tx.size() == txn_max || c->cap + cap[i] > sig_max || c->arena.size() + sz[i] > arena_max) {
+      r = submit(*c);
+      if (!r) r = next(&c);
+      if (r) break;
+    }
+    fdgpu_precompile_t d;
+    d.off = (uint32_t)c->arena.size();
+    d.sz = sz[i];
+    d.sig_cap = cap[i];
+    c->arena.insert(c->arena.end(), payloads + off[i], payloads + off[i] + sz[i]);
+    c->tx.push_back(d);
+    c->items.push_back(i);
+    c->cap += cap[i];
   }
   if (!r) r = submit(*c);
   while (cnt) {                                /* on an error too: no batch is left in the ring */

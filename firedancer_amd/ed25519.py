@@ -48,6 +48,21 @@ POH_NO_MIX = 0xFFFFFFFF       # FDGPU_POH_NO_MIX
 POH_HASH_CNT_MAX = 1 << 20    # FDGPU_POH_HASH_CNT_MAX
 CODE_POH_MISMATCH = -68       # FDGPU_CODE_POH_MISMATCH
 CODE_POH_TOO_LONG = -69       # FDGPU_CODE_POH_TOO_LONG
+# include/fd_precompile_gpu.h
+PRECOMPILE_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("sig_cap", "<u4")])   # fdgpu_precompile_t
+PRECOMPILE_INFO_DTYPE = np.dtype([("instr_idx", "<u2"), ("rec_idx", "<u2"), ("ed_instr_cnt", "<u2"), ("sig_cnt", "<u2"),
+                                  ("ed_code", "i1"), ("_pad", "u1", (7,))])          # fdgpu_precompile_info_t
+PRECOMPILE_WALK_DTYPE = np.dtype([("sig0", "<u4"), ("sig_cnt", "<u2"), ("instr_idx", "<u2"), ("rec_idx", "<u2"),
+                                  ("ed_instr_cnt", "<u2"), ("code", "i1"), ("_pad", "u1", (3,))])   # fdgpu_precompile_walk_t
+CODE_PRECOMPILE_DATA_SIZE = -70     # FDGPU_CODE_PRECOMPILE_DATA_SIZE
+CODE_PRECOMPILE_DATA_OFFSET = -71   # FDGPU_CODE_PRECOMPILE_DATA_OFFSET
+CODE_PRECOMPILE_SIGNATURE = -72     # FDGPU_CODE_PRECOMPILE_SIGNATURE
+CODE_PRECOMPILE_CAP = -73           # FDGPU_CODE_PRECOMPILE_CAP
+
+
+def precompile_sig_bound(sz):
+    """fdgpu_precompile_sig_bound: the most records a transaction of sz bytes can emit."""
+    return int(_lib.lib().fdgpu_precompile_sig_bound(int(sz)))
 
 
 def poh_chunk():
@@ -315,6 +330,35 @@ class VerifyEngine:
     def verify_shreds(self, arena, shreds, expected_version):
         return self.poll_shreds(self.submit_shreds(arena, shreds, expected_version), blocking=True)
 
+    def submit_precompiles(self, arena, txns):
+        """fdgpu_submit_precompiles: raw transactions (PRECOMPILE_DTYPE {off,
+        sz, sig_cap}) parsed, their Ed25519 precompile instructions walked
+        and every record verified on the GPU."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=PRECOMPILE_DTYPE)
+        tk = _lib.lib().fdgpu_submit_precompiles(self._h, arena.ctypes.data, arena.size, txns.ctypes.data, len(txns))
+        if tk < 0:
+            raise RuntimeError(f"fdgpu_submit_precompiles failed ({tk}): {_lib.last_error()}")
+        self._pending[tk] = len(txns)
+        return tk
+
+    def poll_precompiles(self, ticket, blocking=True):
+        """-> (codes int8[n], info PRECOMPILE_INFO_DTYPE[n]) or None while pending."""
+        n = self._pending[ticket]
+        codes = np.zeros(max(n, 1), dtype=np.int8)
+        info = np.zeros(max(n, 1), dtype=PRECOMPILE_INFO_DTYPE)
+        rc = _lib.lib().fdgpu_poll_precompiles(self._h, ticket, codes.ctypes.data, info.ctypes.data,
+                                               1 if blocking else 0)
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise RuntimeError(f"fdgpu_poll_precompiles failed ({rc}): {_lib.last_error()}")
+        del self._pending[ticket]
+        return codes[:n], info[:n]
+
+    def verify_precompiles(self, arena, txns):
+        return self.poll_precompiles(self.submit_precompiles(arena, txns), blocking=True)
+
     def submit_poh(self, arena, entries, sig_offs, hash_cnt_cap):
         """fdgpu_submit_poh: a block's PoH entries (POH_DTYPE; sig_offs: the
         arena offsets of their signatures) hashed, rooted, mixed and compared
@@ -420,6 +464,34 @@ class VerifyEngine:
         self._chk(_lib.lib().fdgpu_debug_shred_time(self._h, arena.ctypes.data, arena.size, shreds.ctypes.data,
                                                     len(shreds), int(expected_version), int(iters), ctypes.byref(a),
                                                     ctypes.byref(v)), "debug_shred_time")
+        return a.value, v.value
+
+    def debug_precompile_walk(self, arena, txns):
+        """The precompile ingest alone -> (walk PRECOMPILE_WALK_DTYPE[n],
+        descs SIG_DESC_DTYPE[k], pos uint32[k]: instr_idx << 16 | rec_idx),
+        k the signature slots taken"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=PRECOMPILE_DTYPE)
+        cap = int(txns["sig_cap"].astype(np.uint64).sum())
+        walk = np.zeros(len(txns), dtype=PRECOMPILE_WALK_DTYPE)
+        descs = np.zeros(max(cap, 1), dtype=SIG_DESC_DTYPE)
+        pos = np.zeros(max(cap, 1), dtype=np.uint32)
+        k = ctypes.c_uint64()
+        self._chk(_lib.lib().fdgpu_debug_precompile_walk(self._h, arena.ctypes.data, arena.size, txns.ctypes.data,
+                                                         len(txns), walk.ctypes.data, descs.ctypes.data,
+                                                         pos.ctypes.data, max(cap, 1), ctypes.byref(k)),
+                  "debug_precompile_walk")
+        return walk, descs[:k.value], pos[:k.value]
+
+    def debug_precompile_time(self, arena, txns, iters=5):
+        """-> (ingest_ms, verify_ms): mean device time of the batch's ingest
+        and of its verify, the batch resident in HBM"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=PRECOMPILE_DTYPE)
+        a, v = ctypes.c_double(), ctypes.c_double()
+        self._chk(_lib.lib().fdgpu_debug_precompile_time(self._h, arena.ctypes.data, arena.size, txns.ctypes.data,
+                                                         len(txns), int(iters), ctypes.byref(a), ctypes.byref(v)),
+                  "debug_precompile_time")
         return a.value, v.value
 
     def debug_poh(self, arena, entries, sig_offs, hash_cnt_cap, grid_waves=0):

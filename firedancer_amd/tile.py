@@ -24,6 +24,8 @@ import numpy as np
 
 from . import _lib
 from .ed25519 import CODE_POH_MISMATCH, CODE_POH_TOO_LONG, POH_DTYPE, POH_NO_MIX, TXN_DTYPE  # noqa: F401
+from .ed25519 import (CODE_PRECOMPILE_CAP, CODE_PRECOMPILE_DATA_OFFSET, CODE_PRECOMPILE_DATA_SIZE,  # noqa: F401
+                      CODE_PRECOMPILE_SIGNATURE, PRECOMPILE_INFO_DTYPE)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 TILE_LIB_PATH = os.environ.get("FDGPU_TILE_LIB") or os.path.join(_HERE, "libfd_verify_tile.so")
@@ -101,6 +103,17 @@ class ShredChk(c.Structure):
     """fdt_shred_chk_t"""
     _fields_ = [("shred_idx", c.c_uint32), ("depth", c.c_uint32), ("proof_off", c.c_uint32),
                 ("leaf_off", c.c_uint32), ("leaf_end", c.c_uint32)]
+
+
+class PrecompileWalk(c.Structure):
+    """fdt_precompile_walk_t"""
+    _fields_ = [("code", c.c_int32), ("rec_cnt", c.c_uint32), ("instr_idx", c.c_uint16), ("rec_idx", c.c_uint16),
+                ("ed_instr_cnt", c.c_uint16), ("_pad", c.c_uint16)]
+
+
+# fdt_precompile_rec_t
+PRECOMPILE_REC_DTYPE = np.dtype([("instr_idx", "<u2"), ("rec_idx", "<u2"), ("sig_off", "<u2"), ("pub_off", "<u2"),
+                                 ("msg_off", "<u2"), ("msg_sz", "<u2")])
 
 
 class Verifier(c.Structure):
@@ -293,6 +306,10 @@ def lib():
         "fdgpu_shreds_verify": (c.c_int, [Verifier, vp, u64, vp, u64, c.c_uint16, u64, vp, vp]),
         "fdgpu_poh_verify_host": (c.c_int, [vp, u64, vp, u64, vp, u64, u64, vp, vp]),
         "fdgpu_block_poh_verify": (c.c_int, [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, u64, u64, vp]),
+        "fdt_precompile_walk": (None, [vp, u64, vp, vp, c.c_uint32, c.POINTER(PrecompileWalk)]),
+        "fdt_precompile_verdict": (c.c_int, [c.POINTER(PrecompileWalk), vp, vp, vp]),
+        "fdgpu_precompiles_verify": (c.c_int, [Verifier, vp, vp, vp, u64, u64, vp, vp]),
+        "fdgpu_block_precompile_verify": (c.c_int, [vp, Verifier, vp, vp, vp, u64, u64, vp, vp]),
         "fdt_shred_check": (c.c_int, [vp, u64, c.c_uint16, c.POINTER(ShredChk)]),
         "fdt_shred_root": (None, [vp, c.POINTER(ShredChk), vp]),
         "fdt_sha256": (None, [vp, u64, vp]),
@@ -1137,6 +1154,78 @@ def block_poh_verify(engine, in_hash, hash_cnt, entry_hash, txn_cnt, payloads, h
     if r:
         raise RuntimeError(f"fdgpu_block_poh_verify failed: {r}")
     return codes[:m]
+
+
+def precompile_walk(payload, rec_cap=None):
+    """fdt_txn_parse + fdt_precompile_walk of one raw transaction ->
+    (walk dict {code, rec_cnt, instr_idx, rec_idx, ed_instr_cnt}, recs
+    PRECOMPILE_REC_DTYPE[min(rec_cnt, rec_cap)]), or None if it does not
+    parse.  The buffer handed over holds exactly len(payload) bytes."""
+    payload = bytes(payload)
+    raw = (c.c_uint8 * max(len(payload), 1)).from_buffer_copy(payload or b"\0")
+    txn = (c.c_uint8 * 856)()
+    if len(payload) > 1232 or not lib().fdt_txn_parse(raw, len(payload), txn, None):
+        return None
+    w = PrecompileWalk()
+    lib().fdt_precompile_walk(raw, len(payload), txn, None, 0, c.byref(w))
+    cap = w.rec_cnt if rec_cap is None else min(int(rec_cap), w.rec_cnt)
+    recs = np.zeros(max(cap, 1), dtype=PRECOMPILE_REC_DTYPE)
+    lib().fdt_precompile_walk(raw, len(payload), txn, recs.ctypes.data, cap, c.byref(w))
+    return ({k: getattr(w, k) for k in ("code", "rec_cnt", "instr_idx", "rec_idx", "ed_instr_cnt")}, recs[:cap])
+
+
+def precompile_verdict(walk, recs, ed_codes):
+    """fdt_precompile_verdict -> (code, info PRECOMPILE_INFO_DTYPE record)"""
+    w = PrecompileWalk(walk["code"], walk["rec_cnt"], walk["instr_idx"], walk["rec_idx"], walk["ed_instr_cnt"], 0)
+    recs = np.ascontiguousarray(recs, dtype=PRECOMPILE_REC_DTYPE)
+    ed = np.ascontiguousarray(ed_codes, dtype=np.int8)
+    if len(recs) != walk["rec_cnt"] or len(ed) != walk["rec_cnt"]:
+        raise ValueError("one record and one code per emitted record")
+    info = np.zeros(1, dtype=PRECOMPILE_INFO_DTYPE)
+    r1, e1 = (recs if len(recs) else np.zeros(1, dtype=PRECOMPILE_REC_DTYPE)), (ed if len(ed) else np.zeros(1, np.int8))
+    code = lib().fdt_precompile_verdict(c.byref(w), r1.ctypes.data, e1.ctypes.data, info.ctypes.data)
+    return code, info[0]
+
+
+def _payload_arrays(payloads):
+    n = len(payloads)
+    sizes = np.array([len(p) for p in payloads], dtype=np.uint32)
+    offs = np.zeros(max(n, 1), dtype=np.uint64)
+    if n:
+        offs[1:n] = np.cumsum(sizes[:-1], dtype=np.uint64)
+    arena = np.frombuffer(b"".join(payloads) + b"\0", dtype=np.uint8)
+    return n, sizes, offs, arena
+
+
+def precompiles_verify(verifier, payloads, batch_max=4096):
+    """Raw transactions' Ed25519 precompile instructions to verdicts over any
+    verifier, walked on the host (fdgpu_precompiles_verify) ->
+    (codes int8[n], info PRECOMPILE_INFO_DTYPE[n])"""
+    n, sizes, offs, arena = _payload_arrays(payloads)
+    codes = np.zeros(max(n, 1), dtype=np.int8)
+    info = np.zeros(max(n, 1), dtype=PRECOMPILE_INFO_DTYPE)
+    r = lib().fdgpu_precompiles_verify(verifier.struct, arena.ctypes.data, offs.ctypes.data, sizes.ctypes.data, n,
+                                       int(batch_max), codes.ctypes.data, info.ctypes.data)
+    if r:
+        raise RuntimeError(f"fdgpu_precompiles_verify failed: {r}")
+    return codes[:n], info[:n]
+
+
+def block_precompile_verify(engine, payloads, batch_txn_max=4096, host_verifier=None):
+    """fdgpu_block_precompile_verify: a block's raw transactions (a list of
+    bytes); those that carry Ed25519 precompile instructions go through the
+    engine (a VerifyEngine), or with engine None through the host path over
+    host_verifier -> (codes int8[n], info PRECOMPILE_INFO_DTYPE[n])"""
+    n, sizes, offs, arena = _payload_arrays(payloads)
+    codes = np.zeros(max(n, 1), dtype=np.int8)
+    info = np.zeros(max(n, 1), dtype=PRECOMPILE_INFO_DTYPE)
+    v = host_verifier.struct if host_verifier is not None else Verifier()
+    r = lib().fdgpu_block_precompile_verify(engine._h if engine is not None else None, v, arena.ctypes.data,
+                                            offs.ctypes.data, sizes.ctypes.data, n, int(batch_txn_max),
+                                            codes.ctypes.data, info.ctypes.data)
+    if r:
+        raise RuntimeError(f"fdgpu_block_precompile_verify failed: {r}")
+    return codes[:n], info[:n]
 
 
 # ------------------------------------------------------------------ tiles

@@ -1,0 +1,118 @@
+/* fd_precompile_gpu.h -- a block's Ed25519 precompile instructions to
+   verdicts on the GPU engine.
+
+   What replay checks of every transaction right beside its own signatures
+   (fd_executor_verify_precompiles, src/flamenco/runtime/fd_executor.c:
+   252-270, called from fd_runtime.c:805-806,865-881): each instruction whose
+   program is Ed25519SigVerify111111111111111111111111111 carries a table of
+   signature records whose offsets point into the data of any instruction of
+   the same transaction, and each record is one fd_ed25519_verify
+   (fd_precompile_ed25519_verify, program/fd_precompiles.c:63-206).  Here all
+   of it runs on the device: the raw transactions go up as one arena, are
+   parsed there, their record tables are walked, every record that resolves
+   becomes one lane of the engine's verify, and one code and one info record
+   per transaction come back.  The rules are those of
+   firedancer_amd/csrc/fdt_precompile.h (the one source the host library
+   libfd_verify_tile.so also compiles, as fdt_precompile_walk /
+   fdt_precompile_verdict).
+
+   Not covered: the secp256k1 precompile (another curve, and Keccak-256);
+   an instruction of KeccakSecp256k11111111111111111111111111111 is skipped
+   like that of any other program.  Feature gates are the caller's.
+
+   An extension of fd_ed25519_gpu.h: same engine, same ring slots, tickets
+   and error codes.  Exported from libfd_ed25519_gpu.so.  Plain C11. */
+#ifndef FD_PRECOMPILE_GPU_H
+#define FD_PRECOMPILE_GPU_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "fd_ed25519_gpu.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* txn = arena[off, off+sz); sig_cap: the signature slots the caller reserves
+   for it (the records of it that resolve, or a bound on them) */
+typedef struct {
+  uint32_t off;
+  uint32_t sz;
+  uint32_t sig_cap;
+} fdgpu_precompile_t;
+
+typedef struct {
+  uint16_t instr_idx;     /* failing instruction, 0xFFFF: none                         */
+  uint16_t rec_idx;       /* failing record in it, 0xFFFF: none / instruction-level    */
+  uint16_t ed_instr_cnt;  /* Ed25519 instructions in the transaction                   */
+  uint16_t sig_cnt;       /* records verified                                          */
+  int8_t   ed_code;       /* fd_ed25519 code of the failing record (SIGNATURE), else 0 */
+  uint8_t  _pad[7];
+} fdgpu_precompile_info_t;                                            /* 16 bytes */
+
+/* The reference maps every failure to -1; the names follow its
+   FD_EXECUTOR_PRECOMPILE_ERR_* constants (fd_executor_err.h). */
+#define FDGPU_CODE_PRECOMPILE_DATA_SIZE   (-70)  /* an Ed25519 instruction's data is too short for its table */
+#define FDGPU_CODE_PRECOMPILE_DATA_OFFSET (-71)  /* a record points outside an instruction's data */
+#define FDGPU_CODE_PRECOMPILE_SIGNATURE   (-72)  /* a record's fd_ed25519_verify failed (info.ed_code says how) */
+#define FDGPU_CODE_PRECOMPILE_CAP         (-73)  /* more records resolve than sig_cap: nothing run */
+
+/* The most records a transaction of sz bytes can send to the verifier: the
+   sig_cap of a caller that has not parsed it (derived at
+   fdt_precompile_sig_bound, fdt_precompile.h). */
+uint32_t fdgpu_precompile_sig_bound( uint64_t sz );
+
+/* A ring batch of n transactions, with fdgpu_submit_shreds' slot semantics:
+   an arena inside a fdgpu_host_register'ed region is uploaded in place by DMA
+   (and must stay unchanged until the poll), any other is staged.  Returns the
+   ticket, FDGPU_ERR_FULL, or FDGPU_ERR_INVAL for a null argument, n above the
+   engine's max_txn, sig_cap summing above its max_sig, a transaction outside
+   the arena or larger than 1232 bytes (FD_TXN_MTU), or an arena beyond
+   max_arena.  n == 0 is a valid empty batch. */
+int64_t fdgpu_submit_precompiles( fdgpu_engine_t * e, uint8_t const * arena, uint64_t arena_sz,
+                                  fdgpu_precompile_t const * txns, uint64_t n );
+
+/* codes[i]: 0 (every Ed25519 instruction of the transaction passes, or it
+   has none), one of the four codes above -- the first failing event in
+   (instruction, record) order, as the reference stops there -- or
+   FDGPU_CODE_PARSE_FAIL for a payload fd_txn_parse rejects.  info (NULL: not
+   wanted): n records; on PARSE_FAIL and CAP {0xFFFF, 0xFFFF, 0, 0, 0}.
+   Returns FDGPU_OK, FDGPU_PENDING (non-blocking) or an error. */
+int fdgpu_poll_precompiles( fdgpu_engine_t * e, int64_t ticket, int8_t * codes, fdgpu_precompile_info_t * info,
+                            int blocking );
+
+/* Diagnostics: synchronous, host pointers, outside the ring. */
+/* What the ingest leaves of transaction i: its signature slots [sig0, sig0 +
+   sig_cnt) of the batch's descriptors, and the structural outcome of its walk
+   -- code 0, DATA_SIZE or DATA_OFFSET at (instr_idx, rec_idx), PARSE_FAIL or
+   CAP (both with no slots and position 0xFFFF, 0xFFFF). */
+typedef struct {
+  uint32_t sig0;
+  uint16_t sig_cnt;
+  uint16_t instr_idx;
+  uint16_t rec_idx;
+  uint16_t ed_instr_cnt;
+  int8_t   code;
+  uint8_t  _pad[3];
+} fdgpu_precompile_walk_t;                                            /* 16 bytes */
+/* the ingest alone: walk n records; descs (NULL: not wanted) 4 u32 per
+   signature slot {msg_off, msg_sz, sig_off, pub_off} (arena offsets) and pos
+   (NULL: not wanted) one u32 each, instr_idx << 16 | rec_idx, both of
+   desc_cap slots (>= the sum of sig_cap); *desc_cnt the slots taken.  Slots
+   are handed out wave by wave, so a transaction's sig0 depends on the order
+   the waves ran in; its slots are contiguous and in record order. */
+int fdgpu_debug_precompile_walk( fdgpu_engine_t * e, uint8_t const * arena, uint64_t arena_sz,
+                                 fdgpu_precompile_t const * txns, uint64_t n, fdgpu_precompile_walk_t * walk,
+                                 uint32_t * descs, uint32_t * pos, uint64_t desc_cap, uint64_t * desc_cnt );
+/* the batch resident on the device: the mean time of its ingest (parse, two
+   walks, descriptors) and of its verify over iters runs each, in ms */
+int fdgpu_debug_precompile_time( fdgpu_engine_t * e, uint8_t const * arena, uint64_t arena_sz,
+                                 fdgpu_precompile_t const * txns, uint64_t n, int iters, double * ingest_ms,
+                                 double * verify_ms );
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* FD_PRECOMPILE_GPU_H */

@@ -43,6 +43,7 @@
 #include "fd_ed25519_gpu.h"
 #include "fd_shred_gpu.h"
 #include "fd_poh_gpu.h"
+#include "fd_precompile_gpu.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -766,6 +767,70 @@ int fdgpu_block_poh_verify( fdgpu_engine_t * e, uint8_t const in_hash[32], uint6
                             uint8_t const * entry_hash, uint32_t const * txn_cnt, uint64_t m,
                             uint8_t const * payloads, uint64_t const * off, uint32_t const * sz, uint64_t n_txn,
                             uint64_t hash_cnt_cap, uint64_t batch_entry_max, int8_t * codes );
+
+/* A block's Ed25519 precompile instructions (fd_precompile_gpu.h), what
+   fd_executor_verify_precompiles (src/flamenco/runtime/fd_executor.c:252-270)
+   checks of every transaction beside its signatures; the rules of
+   firedancer_amd/csrc/fdt_precompile.h compiled for the host.
+
+   fdt_precompile_walk: payload[0, sz) and the fdt_txn_t fdt_txn_parse made of
+   it.  Visits the records of its Ed25519 instructions in order and stores
+   those that resolve, up to rec_cap of them (recs may be NULL with rec_cap
+   0: count only), until the first structural failure.  out->rec_cnt counts
+   all that resolve, stored or not; out->code is 0,
+   FDGPU_CODE_PRECOMPILE_DATA_SIZE at (instr_idx, 0xFFFF) or
+   FDGPU_CODE_PRECOMPILE_DATA_OFFSET at (instr_idx, rec_idx).
+   fdt_precompile_verdict: the transaction's code and info from the walk, its
+   rec_cnt records and their fd_ed25519 codes in order. */
+typedef struct {
+  uint16_t instr_idx, rec_idx;          /* the record: instruction, index in its table */
+  uint16_t sig_off, pub_off, msg_off;   /* payload offsets of its signature, key and message */
+  uint16_t msg_sz;
+} fdt_precompile_rec_t;
+typedef struct {
+  int32_t  code;
+  uint32_t rec_cnt;
+  uint16_t instr_idx, rec_idx;          /* of the structural failure; 0xFFFF: none */
+  uint16_t ed_instr_cnt;                /* Ed25519 instructions in the whole transaction */
+  uint16_t _pad;
+} fdt_precompile_walk_t;
+void fdt_precompile_walk( uint8_t const * payload, uint64_t sz, void const * txn, fdt_precompile_rec_t * recs,
+                              uint32_t rec_cap, fdt_precompile_walk_t * out );
+int  fdt_precompile_verdict( fdt_precompile_walk_t const * walk, fdt_precompile_rec_t const * recs,
+                                 int8_t const * ed_codes, fdgpu_precompile_info_t * info );
+
+/* fdgpu_precompiles_verify: transactions to verdicts over any verifier, the
+   parse and the walk on the host (up to 16 threads): transaction i =
+   payloads[off[i], off[i]+sz[i]).  Every record that resolves is one
+   single-signature item of the verifier, sig | key | message copied into the
+   batch's own arena, in batches of <= batch_max items, two in flight; then
+   the verdict.  A batch is bounded by its item count alone: an item takes 96
+   bytes plus its message (at most 998), so the caller chooses batch_max
+   against the verifier's arena limit -- batch_max * 1094 bytes always fit --
+   and a verifier that rejects a batch fails the whole call with its error.
+   codes[i] and info[i] (NULL: not wanted) as fdgpu_poll_precompiles gives
+   them, FDGPU_CODE_PRECOMPILE_CAP aside (there is no cap).  It is the CPU
+   path, and the host-walk baseline the engine's fdgpu_submit_precompiles is
+   measured against.
+
+   fdgpu_block_precompile_verify: a block's raw transactions in the arrays
+   fdgpu_replay_verify takes.  Each is parsed on the host; those with no
+   Ed25519 instruction get 0, unparseable ones FDGPU_CODE_PARSE_FAIL (both
+   with info {0xFFFF, 0xFFFF, 0, 0, 0}), and the rest are forwarded.
+     e != NULL  they go through fdgpu_submit_precompiles with the walk's exact
+                count as their sig_cap, in ring batches of <= batch_txn_max
+                transactions within the engine's limits, two in flight.
+                v_host is ignored: it may be all zeros.
+     e == NULL  they go through fdgpu_precompiles_verify over v_host, which
+                must then have submit and poll.  batch_txn_max is passed on as
+                that call's batch_max, so on this path it counts the
+                verifier's items -- records, not transactions.
+   Returns 0 or < 0. */
+int fdgpu_precompiles_verify( fdgpu_verifier_t v, uint8_t const * payloads, uint64_t const * off, uint32_t const * sz,
+                              uint64_t n, uint64_t batch_max, int8_t * codes, fdgpu_precompile_info_t * info );
+int fdgpu_block_precompile_verify( fdgpu_engine_t * e, fdgpu_verifier_t v_host, uint8_t const * payloads,
+                                   uint64_t const * off, uint32_t const * sz, uint64_t n_txn, uint64_t batch_txn_max,
+                                   int8_t * codes, fdgpu_precompile_info_t * info );
 
 /* --------------------------------------- process separation (§8(f) row 1) */
 
