@@ -14,6 +14,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_ed25519_gpu.h"
 SHRED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_shred_gpu.h")
 POH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_poh_gpu.h")
 PRECOMPILE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_precompile_gpu.h")
+SECP256K1_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_secp256k1_gpu.h")
 
 _LIB = None
 
@@ -178,6 +179,26 @@ def lib():
     L.fdgpu_debug_precompile_time.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_int, c.POINTER(c.c_double),
                                               c.POINTER(c.c_double)]
     L.fdgpu_debug_precompile_time.restype = c.c_int
+    # include/fd_secp256k1_gpu.h
+    L.fdgpu_secp256k1_sig_bound.argtypes = [c.c_uint64]
+    L.fdgpu_secp256k1_sig_bound.restype = c.c_uint32
+    L.fdgpu_submit_secp256k1.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint32]
+    L.fdgpu_submit_secp256k1.restype = c.c_int64
+    L.fdgpu_poll_secp256k1.argtypes = [vp, c.c_int64, vp, vp, c.c_int]
+    L.fdgpu_poll_secp256k1.restype = c.c_int
+    L.fdgpu_debug_secp256k1_walk.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint32, vp, vp, vp, c.c_uint64,
+                                             c.POINTER(c.c_uint64)]
+    L.fdgpu_debug_secp256k1_walk.restype = c.c_int
+    L.fdgpu_debug_keccak256.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, vp]
+    L.fdgpu_debug_keccak256.restype = c.c_int
+    L.fdgpu_debug_secp256k1_recover.argtypes = [vp, vp, c.c_uint64, vp, vp]
+    L.fdgpu_debug_secp256k1_recover.restype = c.c_int
+    L.fdgpu_debug_secp256k1_time.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint32, c.c_int,
+                                             c.POINTER(c.c_double), c.POINTER(c.c_double)]
+    L.fdgpu_debug_secp256k1_time.restype = c.c_int
+    # the secp256k1 arithmetic's diagnostic (csrc/fdgpu_secp256k1.h)
+    L.fdgpu_debug_secp256k1_ops.argtypes = [vp, vp, c.c_uint64, vp]
+    L.fdgpu_debug_secp256k1_ops.restype = c.c_int
     # the group layer's diagnostics (csrc/fdgpu_internal.h)
     L.fdgpu_debug_fe_raw.argtypes = [vp, vp, c.c_uint64, vp]
     L.fdgpu_debug_ge_ops.argtypes = [vp, vp, c.c_uint64, vp]

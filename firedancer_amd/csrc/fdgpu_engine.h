@@ -1,8 +1,8 @@
 /* fdgpu_engine.h -- what the host engine's units share (fdgpu_engine.cpp, fdgpu_ring.cpp, fdgpu_frags.cpp,
-   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp, fdgpu_shreds.cpp, fdgpu_poh_batch.cpp, fdgpu_precompiles.cpp): the error text, the environment switches,
+   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp, fdgpu_shreds.cpp, fdgpu_poh_batch.cpp, fdgpu_precompiles.cpp, fdgpu_secp256k1s.cpp): the error text, the environment switches,
    the owners of HIP memory, the ring's slot and the engine, the host-side buffer layouts, and the few internals more
    than one unit calls.  Everything here has hidden visibility: the exported C ABI is include/fd_ed25519_gpu.h and its
-   extensions include/fd_shred_gpu.h, include/fd_poh_gpu.h and include/fd_precompile_gpu.h, nothing else (tests/test_abi.py).  The kernels do not include this file. */
+   extensions include/fd_shred_gpu.h, include/fd_poh_gpu.h, include/fd_precompile_gpu.h and include/fd_secp256k1_gpu.h, nothing else (tests/test_abi.py).  The kernels do not include this file. */
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@
 #include "../../include/fd_ed25519_gpu.h"
 #include "../../include/fd_poh_gpu.h"
 #include "../../include/fd_precompile_gpu.h"
+#include "../../include/fd_secp256k1_gpu.h"
 #include "../../include/fd_shred_gpu.h"
 #include "fdgpu_internal.h"
 #include "fdt_parse.h"
@@ -185,6 +186,7 @@ enum class Batch : uint8_t {
   Shred,    /* fdgpu_submit_shreds: item_results() in h_res, the items the roots */
   Poh,      /* fdgpu_submit_poh: item_results() in h_res, the items the hashes */
   Precompile,   /* fdgpu_submit_precompiles: item_results(n, 16) in h_res, the items the infos */
+  Secp256k1,    /* fdgpu_submit_secp256k1: the same */
 };
 
 struct Slot {
@@ -245,7 +247,7 @@ struct Slot {
      tree's nodes (32 B per signature) */
   HostBuf<fdgpu_poh_entry_t> h_pe; DevBuf<fdgpu_poh_entry_t> d_pe;
   HostBuf<uint32_t> h_psig, h_pord; DevBuf<uint32_t> d_psig, d_pord, d_pnodes, d_phead;
-  /* precompile batches (fdgpu_submit_precompiles), allocated on the slot's first one for max_txn transactions and
+  /* precompile batches (fdgpu_submit_precompiles, fdgpu_submit_secp256k1), allocated on the slot's first one for max_txn transactions and
      max_sig signatures: the records, the ingest's signature count, the parsed fd_txn_t records (FDT_TXN_MAX_SZ_BYTES
      each), the walks' outcomes and the signatures' positions */
   HostBuf<fdgpu_precompile_t> h_pc; DevBuf<fdgpu_precompile_t> d_pc;
@@ -348,6 +350,11 @@ int64_t slot_publish(fdgpu_engine_t *e, Slot *s, Batch kind, uint64_t txn_cnt, u
    batch's hashes, a precompile batch's infos) */
 int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking, bool keep, uint8_t *trailers = nullptr,
               uint64_t *tags = nullptr, uint16_t *out_szs = nullptr, uint8_t *items = nullptr);
+
+/* fdgpu_precompiles.cpp: what both precompile batch kinds (fdgpu_precompiles.cpp, fdgpu_secp256k1s.cpp) share */
+int precompile_args(const fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_precompile_t const *tx,
+                    uint64_t n, uint64_t *sig_cap);
+bool slot_precompile_bufs(Slot &s, const fdgpu_cfg_t &c);
 
 /* fdgpu_frags.cpp */
 int merge_kick(fdgpu_engine_t *e, bool force);

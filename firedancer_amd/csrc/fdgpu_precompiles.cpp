@@ -12,9 +12,7 @@ using namespace fdgpu;
 static_assert(sizeof(fdgpu_precompile_info_t) == 16 && sizeof(fdgpu_precompile_walk_t) == 16 &&
               sizeof(fdgpu_precompile_t) == 12, "the kernels store these as words");
 
-namespace {
-
-constexpr uint64_t INFO_SZ = sizeof(fdgpu_precompile_info_t);
+namespace fdgpu {
 
 /* Checks every argument of a precompile batch; 0 and *sig_cap the signature slots it reserves, or FDGPU_ERR_INVAL
    with the error text set. */
@@ -52,6 +50,12 @@ bool slot_precompile_bufs(Slot &s, const fdgpu_cfg_t &c) {
   HIPCHK(s.d_pc.alloc(n * sizeof(fdgpu_precompile_t)), false);
   return true;
 }
+
+}  // namespace fdgpu
+
+namespace {
+
+constexpr uint64_t INFO_SZ = sizeof(fdgpu_precompile_info_t);
 
 /* a precompile batch resident on the device outside the ring (the diagnostics): synchronous upload */
 struct DevPrecompiles {

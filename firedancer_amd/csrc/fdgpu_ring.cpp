@@ -274,6 +274,7 @@ int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking
       if (items && n) memcpy(items, s->h_res + item_results(n).items, n * 32);
       break;
     case Batch::Precompile:
+    case Batch::Secp256k1:
       if (txn_codes && n) memcpy(txn_codes, s->h_res, n);
       if (items && n) memcpy(items, s->h_res + item_results(n, 16).items, n * 16);
       break;

@@ -20,8 +20,10 @@
                                   failure), else the structural failure, else 0.
    Records behind a structural failure are never emitted, so verifying every
    emitted record rather than stopping at the first bad one changes nothing.
-   The secp256k1 precompile is not restated: its instructions are skipped
-   like those of any other program.
+   The secp256k1 precompile is not restated here: its instructions are
+   skipped like those of any other program.  Its rules are fdt_secp256k1.h's
+   (include/fd_secp256k1_gpu.h), which reuses this file's reader, walk record
+   and verdict rule.
 
    Compiled by g++ into libfd_verify_tile.so (fdt_precompile_walk,
    fdt_precompile_verdict) and by hipcc into fdgpu_precompile_ingest_kernel /

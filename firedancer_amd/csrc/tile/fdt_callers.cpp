@@ -41,6 +41,7 @@
 #include "../../../include/fd_verify_tile.h"
 #include "../fdt_poh.h"
 #include "../fdt_precompile.h"
+#include "../fdt_secp256k1.h"
 #include "../fdt_shred.h"
 
 namespace {
@@ -622,6 +623,258 @@ int fdgpu_block_precompile_verify(fdgpu_engine_t *e, fdgpu_verifier_t v_host, co
     if (d) return r ? r : d;
   }
   return r;
+}
+
+}  // extern "C"
+
+/* ---- secp256k1 precompile ---- */
+
+namespace {
+
+int k1_record(const uint8_t *payload, const fdt_precompile_rec_t &q) {
+  fdt_keccak_plain_reader r{payload};
+  return fdt_secp256k1_record_core(r, q.msg_off, q.msg_sz, q.sig_off, q.pub_off);
+}
+
+void be32_to_u256(fdt_u256 &a, const uint8_t *b) {
+  fdt_keccak_plain_reader r{b};
+  fdt_u256_load_be(a, r, 0);
+}
+
+void u256_to_be32(uint8_t *b, const fdt_u256 &a) {
+  for (int i = 0; i < 8; i++)
+    for (int k = 0; k < 4; k++) b[4 * (7 - i) + k] = (uint8_t)(a.v[i] >> (8 * (3 - k)));
+}
+
+}  // namespace
+
+extern "C" {
+
+void fdt_keccak256(const uint8_t *msg, uint64_t sz, uint8_t *out) { fdt_keccak256_core(msg, sz, out); }
+
+int fdt_secp256k1_recover(const uint8_t *hash, const uint8_t *sig, int recid, uint8_t *key) {
+  fdt_u256 h, r, s, x, y;
+  be32_to_u256(h, hash);
+  be32_to_u256(r, sig);
+  be32_to_u256(s, sig + 32);
+  const int rc = fdt_secp256k1_recover_core(h, r, s, (uint32_t)recid, x, y);
+  u256_to_be32(key, x);
+  u256_to_be32(key + 32, y);
+  return rc;
+}
+
+void fdt_secp256k1_walk(const uint8_t *payload, uint64_t sz, const void *txn, uint32_t flags, fdt_precompile_rec_t *recs,
+                        uint32_t rec_cap, fdt_precompile_walk_t *out) {
+  rec_store st{recs, recs ? rec_cap : 0u};
+  fdt_secp256k1_walk_core(payload, sz, (const fdt_txn_t *)txn, flags, st, out);
+}
+
+int fdt_secp256k1_record(const uint8_t *payload, uint64_t sz, const fdt_precompile_rec_t *rec) {
+  (void)sz;
+  return k1_record(payload, *rec);
+}
+
+int fdt_secp256k1_verdict(const fdt_precompile_walk_t *walk, const fdt_precompile_rec_t *recs, const int8_t *codes,
+                          fdgpu_precompile_info_t *info) {
+  fdgpu_precompile_info_t tmp;
+  return fdt_secp256k1_verdict_core(
+      walk->code, walk->instr_idx, walk->rec_idx, walk->ed_instr_cnt, walk->rec_cnt,
+      [&](uint32_t k) { return (int)codes[k]; },
+      [&](uint32_t k) { return ((uint32_t)recs[k].instr_idx << 16) | recs[k].rec_idx; }, info ? info : &tmp);
+}
+
+int fdgpu_secp256k1_verify_host(const uint8_t *payloads, const uint64_t *off, const uint32_t *sz, uint64_t n, uint32_t flags,
+                                int8_t *codes, fdgpu_precompile_info_t *info) {
+  if (!codes || (n && (!payloads || !off || !sz))) return FDGPU_ERR_INVAL;
+  /* the walks first, then the records -- the expensive part -- dealt over the threads one by one */
+  std::vector<fdt_precompile_walk_t> walk(std::max<uint64_t>(n, 1));
+  std::vector<uint8_t> parsed(std::max<uint64_t>(n, 1));
+  std::vector<uint64_t> rec0(n + 1, 0);
+  auto one = [&](uint64_t i, fdt_precompile_rec_t *recs, uint32_t cap) {
+    alignas(8) uint8_t txn_buf[FDT_TXN_MAX_SZ];
+    const uint8_t *raw = payloads + off[i];
+    parsed[i] = sz[i] <= FDT_TXN_MTU && fdt_txn_parse(raw, sz[i], txn_buf, nullptr) != 0;
+    if (parsed[i]) fdt_secp256k1_walk(raw, sz[i], txn_buf, flags, recs, cap, &walk[i]);
+    else walk[i] = {FDGPU_CODE_PARSE_FAIL, 0, 0xFFFF, 0xFFFF, 0, 0};
+  };
+  par_for(n, [&](uint64_t i) { one(i, nullptr, 0); });
+  for (uint64_t i = 0; i < n; i++) rec0[i + 1] = rec0[i] + walk[i].rec_cnt;
+  const uint64_t total = rec0[n];
+  std::vector<fdt_precompile_rec_t> recs(std::max<uint64_t>(total, 1));
+  std::vector<uint32_t> owner(std::max<uint64_t>(total, 1));
+  par_for(n, [&](uint64_t i) {
+    if (!walk[i].rec_cnt) return;
+    one(i, recs.data() + rec0[i], walk[i].rec_cnt);
+    for (uint64_t k = rec0[i]; k < rec0[i + 1]; k++) owner[k] = (uint32_t)i;
+  });
+  std::vector<int8_t> rc(std::max<uint64_t>(total, 1));
+  {
+    std::atomic<uint64_t> next{0};
+    auto work = [&] {
+      for (uint64_t k; (k = next.fetch_add(1)) < total;) rc[k] = (int8_t)k1_record(payloads + off[owner[k]], recs[k]);
+    };
+    const unsigned hw = std::thread::hardware_concurrency();
+    const uint64_t nt = std::min<uint64_t>({16, hw ? hw : 1, total});
+    std::vector<std::thread> th;
+    for (uint64_t t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+  }
+  for (uint64_t i = 0; i < n; i++) {
+    fdgpu_precompile_info_t tmp;
+    fdgpu_precompile_info_t *o = info ? info + i : &tmp;
+    if (!parsed[i]) { codes[i] = FDGPU_CODE_PARSE_FAIL; *o = INFO_NONE; continue; }
+    codes[i] = (int8_t)fdt_secp256k1_verdict(&walk[i], recs.data() + rec0[i], rc.data() + rec0[i], o);
+  }
+  return 0;
+}
+
+int fdgpu_block_secp256k1_verify(fdgpu_engine_t *e, const uint8_t *payloads, const uint64_t *off, const uint32_t *sz,
+                                 uint64_t n_txn, uint32_t flags, uint64_t batch_txn_max, int8_t *codes,
+                                 fdgpu_precompile_info_t *info) {
+  if (!codes || !batch_txn_max || (n_txn && (!payloads || !off || !sz))) return FDGPU_ERR_INVAL;
+  /* the host's part: which transactions carry a secp256k1 instruction, and how many record slots each needs */
+  std::vector<uint32_t> cap(std::max<uint64_t>(n_txn, 1));
+  std::vector<uint8_t> fwd(std::max<uint64_t>(n_txn, 1));
+  par_for(n_txn, [&](uint64_t i) {
+    alignas(8) uint8_t txn_buf[FDT_TXN_MAX_SZ];
+    const uint8_t *raw = payloads + off[i];
+    fwd[i] = 0;
+    if (sz[i] > FDT_TXN_MTU || !fdt_txn_parse(raw, sz[i], txn_buf, nullptr)) {
+      codes[i] = FDGPU_CODE_PARSE_FAIL;
+      if (info) info[i] = INFO_NONE;
+      return;
+    }
+    fdt_precompile_walk_t w;
+    fdt_secp256k1_walk(raw, sz[i], txn_buf, flags, nullptr, 0, &w);
+    if (!w.ed_instr_cnt) {
+      codes[i] = 0;
+      if (info) info[i] = INFO_NONE;
+      return;
+    }
+    fwd[i] = 1;
+    cap[i] = w.rec_cnt;
+  });
+  std::vector<uint64_t> idx;
+  for (uint64_t i = 0; i < n_txn; i++) if (fwd[i]) idx.push_back(i);
+  if (idx.empty()) return 0;
+  if (!e) {
+    std::vector<uint64_t> o2(idx.size());
+    std::vector<uint32_t> s2(idx.size());
+    std::vector<int8_t> c2(idx.size());
+    std::vector<fdgpu_precompile_info_t> i2(idx.size());
+    for (size_t k = 0; k < idx.size(); k++) { o2[k] = off[idx[k]]; s2[k] = sz[idx[k]]; }
+    const int r = fdgpu_secp256k1_verify_host(payloads, o2.data(), s2.data(), idx.size(), flags, c2.data(), i2.data());
+    if (r) return r;
+    for (size_t k = 0; k < idx.size(); k++) { codes[idx[k]] = c2[k]; if (info) info[idx[k]] = i2[k]; }
+    return 0;
+  }
+  uint64_t txn_max = 0, sig_max = 0, arena_max = 0;
+  if (fdgpu_poh_limits(e, &txn_max, &sig_max, &arena_max)) return FDGPU_ERR_INVAL;
+  txn_max = std::min(txn_max, batch_txn_max);
+  /* a batch: the forwarded payloads copied into an arena of the batch's own; two in flight */
+  struct K1Chunk {
+    std::vector<uint8_t> arena;
+    std::vector<fdgpu_precompile_t> tx;
+    std::vector<uint64_t> items;   /* caller's index of each transaction */
+    uint64_t cap = 0;
+    int64_t ticket = -1;
+  } slot[2];
+  int head = 0, cnt = 0;
+  std::vector<int8_t> buf;
+  std::vector<fdgpu_precompile_info_t> ibuf;
+  auto drain_one = [&]() -> int {
+    K1Chunk &c = slot[head];
+    buf.resize(std::max<size_t>(c.tx.size(), 1));
+    ibuf.resize(std::max<size_t>(c.tx.size(), 1));
+    const int r = fdgpu_poll_secp256k1(e, c.ticket, buf.data(), ibuf.data(), 1);
+    if (r != FDGPU_OK) return r < 0 ? r : FDGPU_ERR_DEVICE;
+    for (size_t i = 0; i < c.items.size(); i++) { codes[c.items[i]] = buf[i]; if (info) info[c.items[i]] = ibuf[i]; }
+    head ^= 1;
+    cnt--;
+    return 0;
+  };
+  auto next = [&](K1Chunk **out) -> int {
+    if (cnt == 2) {
+      const int r = drain_one();
+      if (r) return r;
+    }
+    K1Chunk &c = slot[(head + cnt) & 1];
+    c.arena.clear(); c.tx.clear(); c.items.clear(); c.cap = 0;
+    *out = &c;
+    return 0;
+  };
+  auto submit = [&](K1Chunk &c) -> int {
+    if (c.tx.empty()) return 0;
+    int64_t tk;
+    while ((tk = fdgpu_submit_secp256k1(e, c.arena.data(), c.arena.size(), c.tx.data(), c.tx.size(), flags)) == FDGPU_ERR_FULL) {
+      if (!cnt) return FDGPU_ERR_FULL;
+      const int r = drain_one();
+      if (r) return r;
+    }
+    if (tk < 0) return (int)tk;
+    c.ticket = tk;
+    cnt++;
+    return 0;
+  };
+  K1Chunk *c = nullptr;
+  int r = next(&c);
+  for (size_t k = 0; k < idx.size() && !r; k++) {
+    const uint64_t i = idx[k];
+    if (cap[i] > sig_max || sz[i] > arena_max) { r = FDGPU_ERR_INVAL; break; }   /* one transaction no batch can hold */
+    if (c->tx.size() == txn_max || c->cap + cap[i] > sig_max || c->arena.size() + sz[i] > arena_max) {
+      r = submit(*c);
+      if (!r) r = next(&c);
+      if (r) break;
+    }
+    fdgpu_precompile_t d;
+    d.off = (uint32_t)c->arena.size();
+    d.sz = sz[i];
+    d.sig_cap = cap[i];
+    c->arena.insert(c->arena.end(), payloads + off[i], payloads + off[i] + sz[i]);
+    c->tx.push_back(d);
+    c->items.push_back(i);
+    c->cap += cap[i];
+  }
+  if (!r) r = submit(*c);
+  while (cnt) {                                /* on an error too: no batch is left in the ring */
+    const int d = drain_one();
+    if (d) return r ? r : d;
+  }
+  return r;
+}
+
+int fdgpu_precompile_merge(int ed_code, const fdgpu_precompile_info_t *ed_info, int k1_code,
+                           const fdgpu_precompile_info_t *k1_info, fdgpu_precompile_info_t *out) {
+  fdgpu_precompile_info_t tmp;
+  fdgpu_precompile_info_t *o = out ? out : &tmp;
+  const fdgpu_precompile_info_t a = ed_info ? *ed_info : INFO_NONE, b = k1_info ? *k1_info : INFO_NONE;
+  *o = INFO_NONE;
+  if (ed_code == FDGPU_CODE_PARSE_FAIL || k1_code == FDGPU_CODE_PARSE_FAIL) return FDGPU_CODE_PARSE_FAIL;
+  if (ed_code == FDGPU_CODE_PRECOMPILE_CAP || k1_code == FDGPU_CODE_PRECOMPILE_CAP) return FDGPU_CODE_PRECOMPILE_CAP;
+  /* the first failing instruction of either program (fd_executor.c:255-267); an instruction has one program, so
+     two failures never share an index */
+  const int which = !ed_code && !k1_code ? 0 : !k1_code ? 1 : !ed_code ? 2 : a.instr_idx <= b.instr_idx ? 1 : 2;
+  const fdgpu_precompile_info_t &w = which == 2 ? b : a;
+  if (which) { o->instr_idx = w.instr_idx; o->rec_idx = w.rec_idx; o->ed_code = w.ed_code; }
+  o->ed_instr_cnt = (uint16_t)(a.ed_instr_cnt + b.ed_instr_cnt);
+  o->sig_cnt = (uint16_t)(a.sig_cnt + b.sig_cnt);
+  o->_pad[0] = (uint8_t)which;
+  return which == 0 ? 0 : which == 1 ? ed_code : k1_code;
+}
+
+int fdgpu_block_precompile_verify_all(fdgpu_engine_t *e, fdgpu_verifier_t v_host, const uint8_t *payloads, const uint64_t *off,
+                                      const uint32_t *sz, uint64_t n_txn, uint32_t flags, uint64_t batch_txn_max,
+                                      int8_t *codes, fdgpu_precompile_info_t *info) {
+  if (!codes) return FDGPU_ERR_INVAL;
+  std::vector<int8_t> c1(std::max<uint64_t>(n_txn, 1)), c2(std::max<uint64_t>(n_txn, 1));
+  std::vector<fdgpu_precompile_info_t> i1(std::max<uint64_t>(n_txn, 1)), i2(std::max<uint64_t>(n_txn, 1));
+  int r = fdgpu_block_precompile_verify(e, v_host, payloads, off, sz, n_txn, batch_txn_max, c1.data(), i1.data());
+  if (!r) r = fdgpu_block_secp256k1_verify(e, payloads, off, sz, n_txn, flags, batch_txn_max, c2.data(), i2.data());
+  if (r) return r;
+  for (uint64_t i = 0; i < n_txn; i++)
+    codes[i] = (int8_t)fdgpu_precompile_merge(c1[i], &i1[i], c2[i], &i2[i], info ? info + i : nullptr);
+  return 0;
 }
 
 }  // extern "C"

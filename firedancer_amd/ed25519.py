@@ -60,6 +60,21 @@ CODE_PRECOMPILE_SIGNATURE = -72     # FDGPU_CODE_PRECOMPILE_SIGNATURE
 CODE_PRECOMPILE_CAP = -73           # FDGPU_CODE_PRECOMPILE_CAP
 
 
+# include/fd_secp256k1_gpu.h
+SECP256K1_FAIL_ON_BAD_COUNT = 1     # FDGPU_SECP256K1_FAIL_ON_BAD_COUNT
+SECP256K1_ERR_RECID = -1            # FDGPU_SECP256K1_ERR_RECID
+SECP256K1_ERR_RANGE = -2            # FDGPU_SECP256K1_ERR_RANGE
+SECP256K1_ERR_POINT = -3            # FDGPU_SECP256K1_ERR_POINT
+SECP256K1_ERR_INFINITY = -4         # FDGPU_SECP256K1_ERR_INFINITY
+SECP256K1_ERR_ADDRESS = -5          # FDGPU_SECP256K1_ERR_ADDRESS
+SECP256K1_OPS_IN, SECP256K1_OPS_OUT = 49, 17    # csrc/fdgpu_secp256k1.h: words per item of debug_secp256k1_ops
+
+
+def secp256k1_sig_bound(sz):
+    """fdgpu_secp256k1_sig_bound: the most records a transaction of sz bytes can emit."""
+    return int(_lib.lib().fdgpu_secp256k1_sig_bound(int(sz)))
+
+
 def precompile_sig_bound(sz):
     """fdgpu_precompile_sig_bound: the most records a transaction of sz bytes can emit."""
     return int(_lib.lib().fdgpu_precompile_sig_bound(int(sz)))
@@ -359,6 +374,35 @@ class VerifyEngine:
     def verify_precompiles(self, arena, txns):
         return self.poll_precompiles(self.submit_precompiles(arena, txns), blocking=True)
 
+    def submit_secp256k1(self, arena, txns, flags=0):
+        """fdgpu_submit_secp256k1: raw transactions (PRECOMPILE_DTYPE {off,
+        sz, sig_cap}) parsed, their secp256k1 precompile instructions walked
+        and every record checked on the GPU."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=PRECOMPILE_DTYPE)
+        tk = _lib.lib().fdgpu_submit_secp256k1(self._h, arena.ctypes.data, arena.size, txns.ctypes.data, len(txns),
+                                               int(flags))
+        if tk < 0:
+            raise RuntimeError(f"fdgpu_submit_secp256k1 failed ({tk}): {_lib.last_error()}")
+        self._pending[tk] = len(txns)
+        return tk
+
+    def poll_secp256k1(self, ticket, blocking=True):
+        """-> (codes int8[n], info PRECOMPILE_INFO_DTYPE[n]) or None while pending."""
+        n = self._pending[ticket]
+        codes = np.zeros(max(n, 1), dtype=np.int8)
+        info = np.zeros(max(n, 1), dtype=PRECOMPILE_INFO_DTYPE)
+        rc = _lib.lib().fdgpu_poll_secp256k1(self._h, ticket, codes.ctypes.data, info.ctypes.data, 1 if blocking else 0)
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise RuntimeError(f"fdgpu_poll_secp256k1 failed ({rc}): {_lib.last_error()}")
+        del self._pending[ticket]
+        return codes[:n], info[:n]
+
+    def verify_secp256k1(self, arena, txns, flags=0):
+        return self.poll_secp256k1(self.submit_secp256k1(arena, txns, flags), blocking=True)
+
     def submit_poh(self, arena, entries, sig_offs, hash_cnt_cap):
         """fdgpu_submit_poh: a block's PoH entries (POH_DTYPE; sig_offs: the
         arena offsets of their signatures) hashed, rooted, mixed and compared
@@ -492,6 +536,73 @@ class VerifyEngine:
         self._chk(_lib.lib().fdgpu_debug_precompile_time(self._h, arena.ctypes.data, arena.size, txns.ctypes.data,
                                                          len(txns), int(iters), ctypes.byref(a), ctypes.byref(v)),
                   "debug_precompile_time")
+        return a.value, v.value
+
+    def debug_secp256k1_walk(self, arena, txns, flags=0):
+        """The secp256k1 ingest alone -> (walk PRECOMPILE_WALK_DTYPE[n],
+        descs SIG_DESC_DTYPE[k] (pub_off: the address), pos uint32[k]:
+        instr_idx << 16 | rec_idx), k the record slots taken"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=PRECOMPILE_DTYPE)
+        cap = int(txns["sig_cap"].astype(np.uint64).sum())
+        walk = np.zeros(len(txns), dtype=PRECOMPILE_WALK_DTYPE)
+        descs = np.zeros(max(cap, 1), dtype=SIG_DESC_DTYPE)
+        pos = np.zeros(max(cap, 1), dtype=np.uint32)
+        k = ctypes.c_uint64()
+        self._chk(_lib.lib().fdgpu_debug_secp256k1_walk(self._h, arena.ctypes.data, arena.size, txns.ctypes.data,
+                                                        len(txns), int(flags), walk.ctypes.data, descs.ctypes.data,
+                                                        pos.ctypes.data, max(cap, 1), ctypes.byref(k)),
+                  "debug_secp256k1_walk")
+        return walk, descs[:k.value], pos[:k.value]
+
+    def debug_keccak256(self, msgs):
+        """Keccak-256 of each of msgs (bytes, at most 1232 each), one per lane -> uint8[n, 32]"""
+        arena = np.frombuffer(b"".join(msgs) + b"\0", dtype=np.uint8)
+        os_ = np.zeros((len(msgs), 2), dtype=np.uint32)
+        at = 0
+        for i, m in enumerate(msgs):
+            os_[i] = (at, len(m))
+            at += len(m)
+        out = np.zeros((len(msgs), 32), dtype=np.uint8)
+        self._chk(_lib.lib().fdgpu_debug_keccak256(self._h, arena.ctypes.data, arena.size - 1, os_.ctypes.data, len(msgs),
+                                                   out.ctypes.data), "debug_keccak256")
+        return out
+
+    def debug_secp256k1_recover(self, items):
+        """items: (hash32, sig64, recid) -> (codes int8[n], keys uint8[n, 64])"""
+        buf = np.frombuffer(b"".join(bytes(h) + bytes(s) + bytes([r & 0xFF]) for h, s, r in items), dtype=np.uint8)
+        if buf.size != 97 * len(items):
+            raise ValueError("each item is 32 + 64 bytes and a recovery id")
+        codes = np.zeros(len(items), dtype=np.int8)
+        keys = np.zeros((len(items), 64), dtype=np.uint8)
+        self._chk(_lib.lib().fdgpu_debug_secp256k1_recover(self._h, buf.ctypes.data, len(items), codes.ctypes.data,
+                                                           keys.ctypes.data), "debug_secp256k1_recover")
+        return codes, keys
+
+    def debug_secp256k1_ops(self, items):
+        """items: (op, a, b, c, d, e, f) of integers below 2^256 (missing
+        ones 0); the operations are listed at fdgpu_debug_secp256k1_ops
+        (csrc/fdgpu_secp256k1.h) -> [(flag, x, y)] as integers"""
+        buf = np.zeros((len(items), SECP256K1_OPS_IN), dtype=np.uint32)
+        for i, it in enumerate(items):
+            buf[i, 0] = it[0]
+            for k, v in enumerate(it[1:]):
+                buf[i, 1 + 8 * k:9 + 8 * k] = [(v >> (32 * j)) & 0xFFFFFFFF for j in range(8)]
+        out = np.zeros((len(items), SECP256K1_OPS_OUT), dtype=np.uint32)
+        self._chk(_lib.lib().fdgpu_debug_secp256k1_ops(self._h, buf.ctypes.data, len(items), out.ctypes.data),
+                  "debug_secp256k1_ops")
+        val = lambda w: sum(int(x) << (32 * j) for j, x in enumerate(w))
+        return [(int(o[0]), val(o[1:9]), val(o[9:17])) for o in out]
+
+    def debug_secp256k1_time(self, arena, txns, flags=0, iters=5):
+        """-> (ingest_ms, recover_ms): mean device time of the batch's ingest
+        and of its recover kernel, the batch resident in HBM"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        txns = np.ascontiguousarray(txns, dtype=PRECOMPILE_DTYPE)
+        a, v = ctypes.c_double(), ctypes.c_double()
+        self._chk(_lib.lib().fdgpu_debug_secp256k1_time(self._h, arena.ctypes.data, arena.size, txns.ctypes.data,
+                                                        len(txns), int(flags), int(iters), ctypes.byref(a),
+                                                        ctypes.byref(v)), "debug_secp256k1_time")
         return a.value, v.value
 
     def debug_poh(self, arena, entries, sig_offs, hash_cnt_cap, grid_waves=0):

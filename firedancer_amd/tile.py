@@ -310,6 +310,15 @@ def lib():
         "fdt_precompile_verdict": (c.c_int, [c.POINTER(PrecompileWalk), vp, vp, vp]),
         "fdgpu_precompiles_verify": (c.c_int, [Verifier, vp, vp, vp, u64, u64, vp, vp]),
         "fdgpu_block_precompile_verify": (c.c_int, [vp, Verifier, vp, vp, vp, u64, u64, vp, vp]),
+        "fdt_keccak256": (None, [vp, u64, vp]),
+        "fdt_secp256k1_recover": (c.c_int, [vp, vp, c.c_int, vp]),
+        "fdt_secp256k1_walk": (None, [vp, u64, vp, c.c_uint32, vp, c.c_uint32, c.POINTER(PrecompileWalk)]),
+        "fdt_secp256k1_record": (c.c_int, [vp, u64, vp]),
+        "fdt_secp256k1_verdict": (c.c_int, [c.POINTER(PrecompileWalk), vp, vp, vp]),
+        "fdgpu_secp256k1_verify_host": (c.c_int, [vp, vp, vp, u64, c.c_uint32, vp, vp]),
+        "fdgpu_block_secp256k1_verify": (c.c_int, [vp, vp, vp, vp, u64, c.c_uint32, u64, vp, vp]),
+        "fdgpu_precompile_merge": (c.c_int, [c.c_int, vp, c.c_int, vp, vp]),
+        "fdgpu_block_precompile_verify_all": (c.c_int, [vp, Verifier, vp, vp, vp, u64, c.c_uint32, u64, vp, vp]),
         "fdt_shred_check": (c.c_int, [vp, u64, c.c_uint16, c.POINTER(ShredChk)]),
         "fdt_shred_root": (None, [vp, c.POINTER(ShredChk), vp]),
         "fdt_sha256": (None, [vp, u64, vp]),
@@ -1225,6 +1234,113 @@ def block_precompile_verify(engine, payloads, batch_txn_max=4096, host_verifier=
                                             codes.ctypes.data, info.ctypes.data)
     if r:
         raise RuntimeError(f"fdgpu_block_precompile_verify failed: {r}")
+    return codes[:n], info[:n]
+
+
+def keccak256(msg):
+    """fdt_keccak256 over a buffer of exactly len(msg) bytes -> 32 bytes"""
+    msg = bytes(msg)
+    raw = (c.c_uint8 * max(len(msg), 1)).from_buffer_copy(msg or b"\0")
+    out = (c.c_uint8 * 32)()
+    lib().fdt_keccak256(raw, len(msg), out)
+    return bytes(out)
+
+
+def secp256k1_recover(hash32, sig64, recid):
+    """fdt_secp256k1_recover -> (code, key[64])"""
+    key = (c.c_uint8 * 64)()
+    rc = lib().fdt_secp256k1_recover(bytes(hash32), bytes(sig64), int(recid), key)
+    return rc, bytes(key)
+
+
+def secp256k1_walk(payload, flags=0, rec_cap=None):
+    """fdt_txn_parse + fdt_secp256k1_walk of one raw transaction, as
+    precompile_walk (ed_instr_cnt counts the secp256k1 instructions; a
+    record's pub_off is its address), or None if it does not parse."""
+    payload = bytes(payload)
+    raw = (c.c_uint8 * max(len(payload), 1)).from_buffer_copy(payload or b"\0")
+    txn = (c.c_uint8 * 856)()
+    if len(payload) > 1232 or not lib().fdt_txn_parse(raw, len(payload), txn, None):
+        return None
+    w = PrecompileWalk()
+    lib().fdt_secp256k1_walk(raw, len(payload), txn, int(flags), None, 0, c.byref(w))
+    cap = w.rec_cnt if rec_cap is None else min(int(rec_cap), w.rec_cnt)
+    recs = np.zeros(max(cap, 1), dtype=PRECOMPILE_REC_DTYPE)
+    lib().fdt_secp256k1_walk(raw, len(payload), txn, int(flags), recs.ctypes.data, cap, c.byref(w))
+    return ({k: getattr(w, k) for k in ("code", "rec_cnt", "instr_idx", "rec_idx", "ed_instr_cnt")}, recs[:cap])
+
+
+def secp256k1_record(payload, rec):
+    """fdt_secp256k1_record: one record's check over a buffer of exactly len(payload) bytes"""
+    payload = bytes(payload)
+    raw = (c.c_uint8 * max(len(payload), 1)).from_buffer_copy(payload or b"\0")
+    r = np.ascontiguousarray(np.array([rec], dtype=PRECOMPILE_REC_DTYPE))
+    return lib().fdt_secp256k1_record(raw, len(payload), r.ctypes.data)
+
+
+def secp256k1_verdict(walk, recs, codes):
+    """fdt_secp256k1_verdict -> (code, info PRECOMPILE_INFO_DTYPE record)"""
+    w = PrecompileWalk(walk["code"], walk["rec_cnt"], walk["instr_idx"], walk["rec_idx"], walk["ed_instr_cnt"], 0)
+    recs = np.ascontiguousarray(recs, dtype=PRECOMPILE_REC_DTYPE)
+    cd = np.ascontiguousarray(codes, dtype=np.int8)
+    if len(recs) != walk["rec_cnt"] or len(cd) != walk["rec_cnt"]:
+        raise ValueError("one record and one code per emitted record")
+    info = np.zeros(1, dtype=PRECOMPILE_INFO_DTYPE)
+    r1, c1 = (recs if len(recs) else np.zeros(1, dtype=PRECOMPILE_REC_DTYPE)), (cd if len(cd) else np.zeros(1, np.int8))
+    code = lib().fdt_secp256k1_verdict(c.byref(w), r1.ctypes.data, c1.ctypes.data, info.ctypes.data)
+    return code, info[0]
+
+
+def secp256k1_verify_host(payloads, flags=0):
+    """fdgpu_secp256k1_verify_host: raw transactions' secp256k1 precompile
+    instructions to verdicts on the host -> (codes int8[n], info PRECOMPILE_INFO_DTYPE[n])"""
+    n, sizes, offs, arena = _payload_arrays(payloads)
+    codes = np.zeros(max(n, 1), dtype=np.int8)
+    info = np.zeros(max(n, 1), dtype=PRECOMPILE_INFO_DTYPE)
+    r = lib().fdgpu_secp256k1_verify_host(arena.ctypes.data, offs.ctypes.data, sizes.ctypes.data, n, int(flags),
+                                          codes.ctypes.data, info.ctypes.data)
+    if r:
+        raise RuntimeError(f"fdgpu_secp256k1_verify_host failed: {r}")
+    return codes[:n], info[:n]
+
+
+def block_secp256k1_verify(engine, payloads, flags=0, batch_txn_max=4096):
+    """fdgpu_block_secp256k1_verify: a block's raw transactions; those that
+    carry secp256k1 precompile instructions go through the engine (a
+    VerifyEngine), or with engine None through the host path ->
+    (codes int8[n], info PRECOMPILE_INFO_DTYPE[n])"""
+    n, sizes, offs, arena = _payload_arrays(payloads)
+    codes = np.zeros(max(n, 1), dtype=np.int8)
+    info = np.zeros(max(n, 1), dtype=PRECOMPILE_INFO_DTYPE)
+    r = lib().fdgpu_block_secp256k1_verify(engine._h if engine is not None else None, arena.ctypes.data,
+                                           offs.ctypes.data, sizes.ctypes.data, n, int(flags), int(batch_txn_max),
+                                           codes.ctypes.data, info.ctypes.data)
+    if r:
+        raise RuntimeError(f"fdgpu_block_secp256k1_verify failed: {r}")
+    return codes[:n], info[:n]
+
+
+def precompile_merge(ed_code, ed_info, k1_code, k1_info):
+    """fdgpu_precompile_merge -> (code, info PRECOMPILE_INFO_DTYPE record; _pad[0]: which program failed)"""
+    a = np.ascontiguousarray(np.array([ed_info], dtype=PRECOMPILE_INFO_DTYPE))
+    b = np.ascontiguousarray(np.array([k1_info], dtype=PRECOMPILE_INFO_DTYPE))
+    out = np.zeros(1, dtype=PRECOMPILE_INFO_DTYPE)
+    code = lib().fdgpu_precompile_merge(int(ed_code), a.ctypes.data, int(k1_code), b.ctypes.data, out.ctypes.data)
+    return code, out[0]
+
+
+def block_precompile_verify_all(engine, payloads, flags=0, batch_txn_max=4096, host_verifier=None):
+    """fdgpu_block_precompile_verify_all: both precompiles over a block, merged
+    -> (codes int8[n], info PRECOMPILE_INFO_DTYPE[n])"""
+    n, sizes, offs, arena = _payload_arrays(payloads)
+    codes = np.zeros(max(n, 1), dtype=np.int8)
+    info = np.zeros(max(n, 1), dtype=PRECOMPILE_INFO_DTYPE)
+    v = host_verifier.struct if host_verifier is not None else Verifier()
+    r = lib().fdgpu_block_precompile_verify_all(engine._h if engine is not None else None, v, arena.ctypes.data,
+                                                offs.ctypes.data, sizes.ctypes.data, n, int(flags), int(batch_txn_max),
+                                                codes.ctypes.data, info.ctypes.data)
+    if r:
+        raise RuntimeError(f"fdgpu_block_precompile_verify_all failed: {r}")
     return codes[:n], info[:n]
 
 

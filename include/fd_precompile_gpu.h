@@ -16,9 +16,12 @@
    libfd_verify_tile.so also compiles, as fdt_precompile_walk /
    fdt_precompile_verdict).
 
-   Not covered: the secp256k1 precompile (another curve, and Keccak-256);
-   an instruction of KeccakSecp256k11111111111111111111111111111 is skipped
-   like that of any other program.  Feature gates are the caller's.
+   Not covered by a batch of this kind: the secp256k1 precompile (another
+   curve, and Keccak-256); an instruction of
+   KeccakSecp256k11111111111111111111111111111 is skipped like that of any
+   other program.  Those are fd_secp256k1_gpu.h's batches, and
+   fd_verify_tile.h's fdgpu_precompile_merge joins the two verdicts.  Feature
+   gates are the caller's.
 
    An extension of fd_ed25519_gpu.h: same engine, same ring slots, tickets
    and error codes.  Exported from libfd_ed25519_gpu.so.  Plain C11. */
