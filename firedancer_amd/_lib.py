@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FDGPU_LIB") or os.path.join(_HERE, "libfd_ed25519_gpu.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_ed25519_gpu.h")
 SHRED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_shred_gpu.h")
+SHRED_SETS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_shred_sets_gpu.h")
 POH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_poh_gpu.h")
 PRECOMPILE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_precompile_gpu.h")
 SECP256K1_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fd_secp256k1_gpu.h")
@@ -152,6 +153,14 @@ def lib():
     L.fdgpu_debug_shred_time.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint16, c.c_int,
                                          c.POINTER(c.c_double), c.POINTER(c.c_double)]
     L.fdgpu_debug_shred_time.restype = c.c_int
+    # include/fd_shred_sets_gpu.h
+    L.fdgpu_submit_shred_sets.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint16]
+    L.fdgpu_submit_shred_sets.restype = c.c_int64
+    L.fdgpu_poll_shred_sets.argtypes = [vp, c.c_int64, vp, vp, vp, c.POINTER(c.c_uint64), c.c_int]
+    L.fdgpu_poll_shred_sets.restype = c.c_int
+    L.fdgpu_debug_shred_sets_time.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, c.c_uint16, c.c_int,
+                                              c.POINTER(c.c_double), c.POINTER(c.c_double)]
+    L.fdgpu_debug_shred_sets_time.restype = c.c_int
     # include/fd_poh_gpu.h
     L.fdgpu_submit_poh.argtypes = [vp, vp, c.c_uint64, vp, c.c_uint64, vp, c.c_uint64, c.c_uint64]
     L.fdgpu_submit_poh.restype = c.c_int64

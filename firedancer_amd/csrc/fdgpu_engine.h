@@ -1,8 +1,8 @@
 /* fdgpu_engine.h -- what the host engine's units share (fdgpu_engine.cpp, fdgpu_ring.cpp, fdgpu_frags.cpp,
-   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp, fdgpu_shreds.cpp, fdgpu_poh_batch.cpp, fdgpu_precompiles.cpp, fdgpu_secp256k1s.cpp): the error text, the environment switches,
+   fdgpu_expand.cpp, fdgpu_dev_batch.cpp, fdgpu_sync.cpp, fdgpu_diag.cpp, fdgpu_shreds.cpp, fdgpu_shred_sets.cpp, fdgpu_poh_batch.cpp, fdgpu_precompiles.cpp, fdgpu_secp256k1s.cpp): the error text, the environment switches,
    the owners of HIP memory, the ring's slot and the engine, the host-side buffer layouts, and the few internals more
    than one unit calls.  Everything here has hidden visibility: the exported C ABI is include/fd_ed25519_gpu.h and its
-   extensions include/fd_shred_gpu.h, include/fd_poh_gpu.h, include/fd_precompile_gpu.h and include/fd_secp256k1_gpu.h, nothing else (tests/test_abi.py).  The kernels do not include this file. */
+   extensions include/fd_shred_gpu.h, include/fd_shred_sets_gpu.h, include/fd_poh_gpu.h, include/fd_precompile_gpu.h and include/fd_secp256k1_gpu.h, nothing else (tests/test_abi.py).  The kernels do not include this file. */
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,6 +23,7 @@
 #include "../../include/fd_precompile_gpu.h"
 #include "../../include/fd_secp256k1_gpu.h"
 #include "../../include/fd_shred_gpu.h"
+#include "../../include/fd_shred_sets_gpu.h"
 #include "fdgpu_internal.h"
 #include "fdt_parse.h"
 
@@ -167,6 +168,14 @@ inline ItemResults item_results(uint64_t n, uint64_t item_sz = 32) {
   return {cb, cb + n * item_sz};
 }
 
+/* A set batch's results for n shreds (fdgpu_submit_shred_sets), in the slot's d_sres and its pinned read-back h_sres:
+   [codes, padded to 64][32 B roots][4 B representatives][the lane count, 4 B, and 12 B of padding]. */
+struct SetResults { uint64_t roots, rep, lanes, bytes; };
+inline SetResults set_results(uint64_t n) {
+  const uint64_t cb = (n + 63) & ~63ull;
+  return {cb, cb + 32 * n, cb + 36 * n, cb + 36 * n + 16};
+}
+
 /* A gathered batch's pinned record area for n frags (h_io, read in place by the ingest kernel), each part 64-B
    aligned: the frag records at 0, the payloads' device-side addresses, the re-check pairs {mcache line address, seq},
    the DMA gather's range table.  bytes keeps the 192 B of slack the earlier size formula had, so no allocation
@@ -187,6 +196,7 @@ enum class Batch : uint8_t {
   Poh,      /* fdgpu_submit_poh: item_results() in h_res, the items the hashes */
   Precompile,   /* fdgpu_submit_precompiles: item_results(n, 16) in h_res, the items the infos */
   Secp256k1,    /* fdgpu_submit_secp256k1: the same */
+  ShredSets,    /* fdgpu_submit_shred_sets: set_results() in h_sres */
 };
 
 struct Slot {
@@ -242,6 +252,13 @@ struct Slot {
      ingest's signature count */
   HostBuf<fdgpu_shred_t> h_sh; DevBuf<fdgpu_shred_t> d_sh;
   DevBuf<uint32_t> d_sh_cnt;
+  /* set batches (fdgpu_submit_shred_sets), allocated on the slot's first one for max_txn shreds: the records, the
+     states, the dedup's table (a power of two >= 2 (max_txn + 1) words), the representatives' descriptor slots, the
+     dedup's signature count, and set_results() with its pinned read-back */
+  HostBuf<fdgpu_set_shred_t> h_set; DevBuf<fdgpu_set_shred_t> d_set;
+  DevBuf<uint8_t> d_set_state;
+  DevBuf<uint32_t> d_set_ht, d_set_slot, d_set_cnt;
+  DevBuf<uint8_t> d_sres; HostBuf<uint8_t> h_sres;
   /* PoH batches (fdgpu_submit_poh), allocated on the slot's first one for max_txn entries and max_sig signatures:
      the entries, the signatures' arena offsets, the queue (entry indices, longest chain first) and its head, and the
      tree's nodes (32 B per signature) */
@@ -346,10 +363,11 @@ int slot_upload(fdgpu_engine_t *e, Slot *s, uint8_t const *arena, uint64_t arena
 int slot_signal(fdgpu_engine_t *e, Slot *s);
 int64_t slot_publish(fdgpu_engine_t *e, Slot *s, Batch kind, uint64_t txn_cnt, uint64_t tr_sz, uint64_t tr_base,
                      bool signal_deferred = false);
-/* the poll of every batch kind: what the kind does not produce stays unwritten (items: a shred batch's roots, a PoH
-   batch's hashes, a precompile batch's infos) */
+/* the poll of every batch kind: what the kind does not produce stays unwritten (items: a shred or set batch's roots, a
+   PoH batch's hashes, a precompile batch's infos; rep, lanes: a set batch's representatives and lane count) */
 int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking, bool keep, uint8_t *trailers = nullptr,
-              uint64_t *tags = nullptr, uint16_t *out_szs = nullptr, uint8_t *items = nullptr);
+              uint64_t *tags = nullptr, uint16_t *out_szs = nullptr, uint8_t *items = nullptr, uint32_t *rep = nullptr,
+              uint64_t *lanes = nullptr);
 
 /* fdgpu_precompiles.cpp: what both precompile batch kinds (fdgpu_precompiles.cpp, fdgpu_secp256k1s.cpp) share */
 int precompile_args(const fdgpu_engine_t *e, uint8_t const *arena, uint64_t arena_sz, fdgpu_precompile_t const *tx,

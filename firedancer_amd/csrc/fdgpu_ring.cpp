@@ -194,7 +194,7 @@ int64_t submit_slot(fdgpu_engine_t *e, Slot *s, uint64_t arena_sz, fdgpu_txn_t c
 namespace fdgpu {
 
 int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking, bool keep, uint8_t *trailers,
-              uint64_t *tags, uint16_t *out_szs, uint8_t *items) {
+              uint64_t *tags, uint16_t *out_szs, uint8_t *items, uint32_t *rep, uint64_t *lanes) {
   if (!e) return FDGPU_ERR_INVAL;
   /* a batch still on the device is answered without the ring lock: the caller owns its ticket's slot until a poll
      returns it done, so the slot's ticket and completion word are stable here; the runtime check below (every 256th
@@ -278,6 +278,14 @@ int poll_slot(fdgpu_engine_t *e, int64_t ticket, int8_t *txn_codes, int blocking
       if (txn_codes && n) memcpy(txn_codes, s->h_res, n);
       if (items && n) memcpy(items, s->h_res + item_results(n, 16).items, n * 16);
       break;
+    case Batch::ShredSets: {
+      const SetResults r = set_results(n);
+      if (txn_codes && n) memcpy(txn_codes, s->h_sres, n);
+      if (items && n) memcpy(items, s->h_sres + r.roots, n * 32);
+      if (rep && n) memcpy(rep, s->h_sres + r.rep, n * 4);
+      if (lanes) { uint32_t l = 0; if (n) memcpy(&l, s->h_sres + r.lanes, 4); *lanes = l; }
+      break;
+    }
   }
   if (keep) st_rlx(s->held, true);
   else st_rlx(s->ticket, (int64_t)-1);

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "../../include/fd_shred_gpu.h"
+#include "../../include/fd_shred_sets_gpu.h"
 #include "fdgpu_internal.h"
 
 #ifdef __cplusplus
@@ -32,6 +33,29 @@ hipError_t fdgpu_launch_shred_ingest(uint8_t *d_arena, const fdgpu_shred_t *d_sh
 hipError_t fdgpu_launch_shred_finish(const fdgpu_txn_desc_t *d_tds, uint32_t n, const int8_t *d_sig_codes,
                                      const uint8_t *d_roots, int8_t *d_codes, uint8_t *d_roots_out,
                                      hipStream_t stream);
+/* Set batches (include/fd_shred_sets_gpu.h).
+   Set ingest: shred i through the checks, the leaf and the proof walk as above, its root to d_arena + roots_off + 32 i;
+   d_state[i] = 0 rejected, 1 its root equals the 32 bytes at known_off, 2 it does not, 3 a candidate for a verify lane
+   (no known root).
+   Set dedup: d_ht, ht_slots (a power of two >= 2 n) words all 0xffffffff at the start, is the table of candidate
+   indices keyed by (signature, root, leader key); d_rep_of[i] = the shred that represents candidate i's key (itself
+   after 32 probes), 0xffffffff for any other shred; each representative takes the next signature descriptor {msg = its
+   root, 32 B, sig = the shred, pub = its leader key} -- one atomic add per workgroup on *d_n_sig, which must be zero
+   at the start -- and d_slot_of[i] = that descriptor's index.  The verify then runs from d_sigs and *d_n_sig.
+   Set finish: d_codes[i] = FDGPU_CODE_SHRED_REJECT, 0, FDGPU_CODE_SHRED_ROOT_MISMATCH or the code of its
+   representative's signature; d_roots_out + 32 i (16-B aligned) = its root, zeros when rejected; *d_lanes_out =
+   *d_n_sig. */
+hipError_t fdgpu_launch_shred_set_ingest(uint8_t *d_arena, const fdgpu_set_shred_t *d_shreds, uint32_t n,
+                                         uint16_t expected_version, uint32_t roots_off, uint8_t *d_state,
+                                         hipStream_t stream);
+hipError_t fdgpu_launch_shred_set_dedup(const uint8_t *d_arena, const fdgpu_set_shred_t *d_shreds, uint32_t n,
+                                        uint32_t roots_off, const uint8_t *d_state, uint32_t *d_ht, uint32_t ht_slots,
+                                        uint64_t seed, uint32_t *d_rep_of, uint32_t *d_slot_of, fdgpu_sig_desc_t *d_sigs,
+                                        uint32_t *d_n_sig, hipStream_t stream);
+hipError_t fdgpu_launch_shred_set_finish(const uint8_t *d_state, const uint32_t *d_rep_of, const uint32_t *d_slot_of,
+                                         uint32_t n, const int8_t *d_sig_codes, const uint8_t *d_roots,
+                                         const uint32_t *d_n_sig, int8_t *d_codes, uint8_t *d_roots_out,
+                                         uint32_t *d_lanes_out, hipStream_t stream);
 /* SHA-256 of d_arena[msg_off, +msg_sz) per descriptor: d_out 8 u32 each (the digest's bytes) */
 hipError_t fdgpu_launch_test_sha256(const uint8_t *d_arena, const fdgpu_sig_desc_t *d_msgs, uint32_t n,
                                     uint32_t *d_out, hipStream_t stream);

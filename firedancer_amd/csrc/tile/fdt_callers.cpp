@@ -13,6 +13,10 @@
               fdgpu_shreds_verify starts from the raw shreds: the checks
               before the signature and the SHA-256 Merkle root on the host
               (fdt_shred.h), then the same batched verify;
+              fdgpu_shred_sets_verify takes every shred of the sets
+              (fd_fec_resolver.c:466-484 checks no signature after a set's
+              first): one verify per distinct (signature, root, leader),
+              shreds with a known root compared with it (fd_shred_sets_gpu.h);
      poh      fd_runtime_block_verify_tpool (src/flamenco/runtime/
               fd_runtime.c:2274-2371) hashes every microblock's chain, builds
               the Merkle root of its signatures and mixes it in;
@@ -43,6 +47,7 @@
 #include "../fdt_precompile.h"
 #include "../fdt_secp256k1.h"
 #include "../fdt_shred.h"
+#include "../fdt_shred_sets.h"
 
 namespace {
 
@@ -251,6 +256,70 @@ int fdgpu_shreds_verify(fdgpu_verifier_t v, const uint8_t *arena, uint64_t arena
   if (!r) r = p.submit(*c);
   if (!r) r = p.finish();
   return r;
+}
+
+int fdgpu_shred_sets_verify(fdgpu_verifier_t v, const uint8_t *arena, uint64_t arena_sz, const fdgpu_set_shred_t *shreds,
+                            uint64_t n, uint16_t expected_version, uint64_t batch_max, int8_t *codes, uint8_t *roots,
+                            uint32_t *rep, uint64_t *lanes) {
+  if (!v.submit || !v.poll || !codes || (n && (!arena || !shreds)) || !batch_max) return FDGPU_ERR_INVAL;
+  if (!fdt_shred_sets_args(arena_sz, shreds, n)) return FDGPU_ERR_INVAL;
+  /* the roots first, as fdgpu_shreds_verify: shreds dealt to the threads in runs of 256 */
+  std::vector<uint8_t> own;
+  if (!roots) { own.resize(32 * std::max<uint64_t>(n, 1)); roots = own.data(); }
+  std::vector<uint8_t> ok(std::max<uint64_t>(n, 1));
+  std::atomic<uint64_t> next{0};
+  auto work = [&] {
+    for (uint64_t b; (b = next.fetch_add(256)) < n;)
+      for (uint64_t i = b; i < std::min(n, b + 256); i++) {
+        fdt_shred_chk_t chk;
+        ok[i] = (uint8_t)fdt_shred_check_core(arena + shreds[i].off, shreds[i].sz, expected_version, &chk);
+        if (ok[i]) fdt_shred_root_core(arena + shreds[i].off, &chk, roots + 32 * i);
+        else memset(roots + 32 * i, 0, 32);
+      }
+  };
+  const unsigned hw = std::thread::hardware_concurrency();
+  const uint64_t nt = std::min<uint64_t>({16, hw ? hw : 1, (n + 1023) / 1024});
+  std::vector<std::thread> th;
+  for (uint64_t t = 1; t < nt; t++) th.emplace_back(work);
+  work();
+  for (auto &t : th) t.join();
+  /* the states, and one representative per distinct key: the first shred that carries it */
+  std::vector<uint32_t> own_rep;
+  if (!rep) { own_rep.resize(std::max<uint64_t>(n, 1)); rep = own_rep.data(); }
+  std::vector<uint32_t> reps;
+  fdt_shred_sets_group(arena, shreds, n, ok.data(), roots, codes, rep, reps);
+  if (lanes) *lanes = reps.size();
+  /* the representatives through the verifier: item = sig[64] | pub[32] | root[32], as fdgpu_fec_roots_verify */
+  std::vector<int8_t> rc(std::max<size_t>(reps.size(), 1));
+  Pipe p(v, rc.data());
+  Chunk *c = nullptr;
+  int r = p.next(&c);
+  for (size_t k = 0; k < reps.size() && !r; k++) {
+    const uint64_t i = reps[k];
+    if (c->txns.size() == batch_max) {
+      r = p.submit(*c);
+      if (!r) r = p.next(&c);
+      if (r) break;
+    }
+    const uint32_t base = (uint32_t)c->arena.size();
+    const uint8_t *sh = arena + shreds[i].off, *pk = arena + shreds[i].pub_off;
+    c->arena.insert(c->arena.end(), sh, sh + 64);
+    c->arena.insert(c->arena.end(), pk, pk + 32);
+    c->arena.insert(c->arena.end(), roots + 32 * i, roots + 32 * i + 32);
+    fdgpu_txn_t d;
+    d.sig_off = base;
+    d.pub_off = base + 64;
+    d.msg_off = base + 96;
+    d.msg_sz = 32;
+    d.sig_cnt = 1;
+    c->txns.push_back(d);
+    c->items.push_back(k);
+  }
+  if (!r) r = p.submit(*c);
+  if (!r) r = p.finish();
+  if (r) return r;
+  fdt_shred_sets_scatter(n, rep, reps, rc.data(), codes);
+  return 0;
 }
 
 int fdgpu_poh_verify_host(const uint8_t *arena, uint64_t arena_sz, const fdgpu_poh_entry_t *entries, uint64_t n,

@@ -41,6 +41,10 @@ ARENA_SLACK = 160
 SHRED_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("pub_off", "<u4")])   # fdgpu_shred_t
 CODE_SHRED_REJECT = -67       # FDGPU_CODE_SHRED_REJECT
 SHRED_SZ_MAX = 1228 + 4       # FDGPU_SHRED_SZ_MAX
+# fdgpu_set_shred_t (include/fd_shred_sets_gpu.h)
+SET_SHRED_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("pub_off", "<u4"), ("known_off", "<u4")])
+SHRED_NO_ROOT = 0xFFFFFFFF    # FDGPU_SHRED_NO_ROOT
+CODE_SHRED_ROOT_MISMATCH = -74    # FDGPU_CODE_SHRED_ROOT_MISMATCH
 # fdgpu_poh_entry_t (include/fd_poh_gpu.h)
 POH_DTYPE = np.dtype([("hash_cnt", "<u8"), ("prev_off", "<u4"), ("hash_off", "<u4"), ("sig_first", "<u4"),
                       ("sig_cnt", "<u4"), ("mix_off", "<u4"), ("_pad", "<u4")])
@@ -345,6 +349,41 @@ class VerifyEngine:
     def verify_shreds(self, arena, shreds, expected_version):
         return self.poll_shreds(self.submit_shreds(arena, shreds, expected_version), blocking=True)
 
+    def submit_shred_sets(self, arena, shreds, expected_version):
+        """fdgpu_submit_shred_sets: every shred of a batch (SET_SHRED_DTYPE
+        {off, sz, pub_off, known_off}), one signature verified per distinct
+        (signature, root, leader key), shreds with a known root held against
+        it."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        shreds = np.ascontiguousarray(shreds, dtype=SET_SHRED_DTYPE)
+        tk = _lib.lib().fdgpu_submit_shred_sets(self._h, arena.ctypes.data, arena.size, shreds.ctypes.data, len(shreds),
+                                                int(expected_version))
+        if tk < 0:
+            raise RuntimeError(f"fdgpu_submit_shred_sets failed ({tk}): {_lib.last_error()}")
+        self._pending[tk] = len(shreds)
+        return tk
+
+    def poll_shred_sets(self, ticket, blocking=True, want_rep=True):
+        """-> (codes int8[n], roots uint8[n, 32], rep uint32[n], lanes) or None
+        while pending; want_rep False: rep and lanes are not asked for (None)."""
+        n = self._pending[ticket]
+        codes = np.zeros(max(n, 1), dtype=np.int8)
+        roots = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        rep = np.zeros(max(n, 1), dtype=np.uint32) if want_rep else None
+        lanes = ctypes.c_uint64(0)
+        rc = _lib.lib().fdgpu_poll_shred_sets(self._h, ticket, codes.ctypes.data, roots.ctypes.data,
+                                              rep.ctypes.data if want_rep else None,
+                                              ctypes.byref(lanes) if want_rep else None, 1 if blocking else 0)
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise RuntimeError(f"fdgpu_poll_shred_sets failed ({rc}): {_lib.last_error()}")
+        del self._pending[ticket]
+        return codes[:n], roots[:n], (rep[:n] if want_rep else None), (int(lanes.value) if want_rep else None)
+
+    def verify_shred_sets(self, arena, shreds, expected_version):
+        return self.poll_shred_sets(self.submit_shred_sets(arena, shreds, expected_version), blocking=True)
+
     def submit_precompiles(self, arena, txns):
         """fdgpu_submit_precompiles: raw transactions (PRECOMPILE_DTYPE {off,
         sz, sig_cap}) parsed, their Ed25519 precompile instructions walked
@@ -508,6 +547,17 @@ class VerifyEngine:
         self._chk(_lib.lib().fdgpu_debug_shred_time(self._h, arena.ctypes.data, arena.size, shreds.ctypes.data,
                                                     len(shreds), int(expected_version), int(iters), ctypes.byref(a),
                                                     ctypes.byref(v)), "debug_shred_time")
+        return a.value, v.value
+
+    def debug_shred_sets_time(self, arena, shreds, expected_version, iters=5):
+        """-> (ingest_ms, verify_ms): mean device time of a set batch's ingest
+        and dedup and of its verify, the batch resident in HBM"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        shreds = np.ascontiguousarray(shreds, dtype=SET_SHRED_DTYPE)
+        a, v = ctypes.c_double(), ctypes.c_double()
+        self._chk(_lib.lib().fdgpu_debug_shred_sets_time(self._h, arena.ctypes.data, arena.size, shreds.ctypes.data,
+                                                         len(shreds), int(expected_version), int(iters), ctypes.byref(a),
+                                                         ctypes.byref(v)), "debug_shred_sets_time")
         return a.value, v.value
 
     def debug_precompile_walk(self, arena, txns):

@@ -97,6 +97,9 @@ CODE_PARSE_FAIL, CODE_TRAILER_CAP = -64, -65
 
 SHRED_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("pub_off", "<u4")])   # fdgpu_shred_t
 CODE_SHRED_REJECT = -67
+SET_SHRED_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u4"), ("pub_off", "<u4"), ("known_off", "<u4")])   # fdgpu_set_shred_t
+SHRED_NO_ROOT = 0xFFFFFFFF
+CODE_SHRED_ROOT_MISMATCH = -74
 
 
 class ShredChk(c.Structure):
@@ -304,6 +307,8 @@ def lib():
         "fdgpu_replay_verify": (c.c_int, [Verifier, vp, vp, vp, u64, u64, u64, vp]),
         "fdgpu_fec_roots_verify": (c.c_int, [Verifier, vp, vp, vp, c.c_int, u64, u64, vp]),
         "fdgpu_shreds_verify": (c.c_int, [Verifier, vp, u64, vp, u64, c.c_uint16, u64, vp, vp]),
+        "fdgpu_shred_sets_verify": (c.c_int, [Verifier, vp, u64, vp, u64, c.c_uint16, u64, vp, vp, vp,
+                                              c.POINTER(c.c_uint64)]),
         "fdgpu_poh_verify_host": (c.c_int, [vp, u64, vp, u64, vp, u64, u64, vp, vp]),
         "fdgpu_block_poh_verify": (c.c_int, [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, u64, u64, vp]),
         "fdt_precompile_walk": (None, [vp, u64, vp, vp, c.c_uint32, c.POINTER(PrecompileWalk)]),
@@ -1121,6 +1126,26 @@ def shreds_verify(verifier, arena, shreds, expected_version, batch_max=65536):
     if r:
         raise RuntimeError(f"fdgpu_shreds_verify failed: {r}")
     return codes[:n], roots[:n]
+
+
+def shred_sets_verify(verifier, arena, shreds, expected_version, batch_max=65536):
+    """Every shred of a batch to a verdict over any verifier, one signature
+    per distinct (signature, root, leader key), roots hashed on the host
+    (fdgpu_shred_sets_verify) -> (codes int8[n], roots uint8[n, 32], rep
+    uint32[n], lanes)"""
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    shreds = np.ascontiguousarray(shreds, dtype=SET_SHRED_DTYPE)
+    n = len(shreds)
+    codes = np.zeros(max(n, 1), dtype=np.int8)
+    roots = np.zeros((max(n, 1), 32), dtype=np.uint8)
+    rep = np.zeros(max(n, 1), dtype=np.uint32)
+    lanes = c.c_uint64(0)
+    r = lib().fdgpu_shred_sets_verify(verifier.struct, arena.ctypes.data, arena.size, shreds.ctypes.data, n,
+                                      int(expected_version), batch_max, codes.ctypes.data, roots.ctypes.data,
+                                      rep.ctypes.data, c.byref(lanes))
+    if r:
+        raise RuntimeError(f"fdgpu_shred_sets_verify failed: {r}")
+    return codes[:n], roots[:n], rep[:n], int(lanes.value)
 
 
 def poh_verify_host(arena, entries, sig_offs, hash_cnt_cap):

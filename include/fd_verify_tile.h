@@ -42,6 +42,7 @@
 
 #include "fd_ed25519_gpu.h"
 #include "fd_shred_gpu.h"
+#include "fd_shred_sets_gpu.h"
 #include "fd_poh_gpu.h"
 #include "fd_precompile_gpu.h"
 #include "fd_secp256k1_gpu.h"
@@ -738,6 +739,16 @@ void fdt_sha256( uint8_t const * data, uint64_t sz, uint8_t * out );
    the host-hash baseline it is measured against.  Returns 0 or < 0. */
 int fdgpu_shreds_verify( fdgpu_verifier_t v, uint8_t const * arena, uint64_t arena_sz, fdgpu_shred_t const * shreds,
                          uint64_t n, uint16_t expected_version, uint64_t batch_max, int8_t * codes, uint8_t * roots );
+
+/* Every shred of a batch over any verifier, one signature per FEC set (the rule of fd_shred_sets_gpu.h stated on the
+   host): roots through fdt_shred_root on up to 16 threads, shreds with a known root held against it, the others
+   grouped by their 128 key bytes (signature, root, leader key) in a hash map and one of each group verified, in
+   batches of <= batch_max, two in flight.  codes and roots as fdgpu_poll_shred_sets gives them; rep[i] = the first
+   shred of i's group, UINT32_MAX for a rejected shred or one with a known root; *lanes = the groups.  roots, rep and
+   lanes may be NULL.  It is the CPU path and the baseline of fdgpu_submit_shred_sets.  Returns 0 or < 0. */
+int fdgpu_shred_sets_verify( fdgpu_verifier_t v, uint8_t const * arena, uint64_t arena_sz,
+                             fdgpu_set_shred_t const * shreds, uint64_t n, uint16_t expected_version,
+                             uint64_t batch_max, int8_t * codes, uint8_t * roots, uint32_t * rep, uint64_t * lanes );
 
 /* A block's proof of history (fd_poh_gpu.h), the companion of
    fdgpu_replay_verify for the other half of fd_runtime_block_verify_tpool.
